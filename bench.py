@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py ... --dump-outputs DIR     (also writes what the last timed step computed, DIR/<name>.npy)
 
 Workload (BASELINE.json configs[1] at N=1, configs[2] at N>1): one synthetic read set per GPU,
 10^7 reads x 100 bp from a shared 50 Mbp random genome (20x, 0.5 % substitutions; seeds 42+rank), indexed as
@@ -62,7 +63,14 @@ def parse():
                          "back), one lane per owner so that every rank is the server of one lane and a client in the others; 'both' = one "
                          "after the other on the same indexes, both values in the line, the faster one as the headline")
     ap.add_argument("--workdir", default=os.environ.get("DSM_BENCH_DIR", "/tmp/dsm_bench"))
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step delivered to its caller as DIR/<name>.npy (float32/float64, "
+                         "at most 64 MB in all: exact totals and a seeded sample of the tuples; see write_dump).  The capture runs inside "
+                         "that step, so a run with this flag is for comparing outputs, not for timing")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def build_index(args, rank, dev):
@@ -423,6 +431,177 @@ def server_record(args, dev, local, pydsm):
             "tuples_when_merged_at_the_end": at_end["tuples"], "stream_bytes": int(sum(len(b) for b in streams)), "dtype": "u32"}
 
 
+# --dump-outputs: what the last timed step handed to its caller, reduced to a fixed size so that two builds can be compared file by file
+DUMP_BYTES = 64_000_000 - (64 << 10)  # data bytes of one dump, all ranks together (room left for the .npy headers)
+DUMP_SAMPLE = 1 << 18                  # tuples sampled per rank before the byte budget
+DUMP_HEAD = 1 << 20                    # stream mode: leading bytes kept of each prefix's wire stream
+DUMP_SEED = 0x243F6A8885A308D3
+
+
+def _mix64(x):
+    """splitmix64's finaliser over a uint64 array (wrapping arithmetic; a bijection, so distinct positions get distinct keys)"""
+    import numpy as np
+    x = x ^ (x >> np.uint64(30))
+    x = x * np.uint64(0xBF58476D1CE4E5B9)
+    x = x ^ (x >> np.uint64(27))
+    x = x * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def _cat_rows(a, b):
+    """row-wise concatenation of two column dicts; 2-D columns are zero-padded to the wider of the two"""
+    import numpy as np
+    if a is None:
+        return b
+    out = {}
+    for k in a:
+        x, y = a[k], b[k]
+        if x.ndim == 2 and x.shape[1] != y.shape[1]:
+            w = max(x.shape[1], y.shape[1])
+            x = np.pad(x, ((0, 0), (0, w - x.shape[1])))
+            y = np.pad(y, ((0, 0), (0, w - y.shape[1])))
+        out[k] = np.concatenate([x, y])
+    return out
+
+
+def _take(rows, idx):
+    return {k: v[idx] for k, v in rows.items()}
+
+
+class TupleSample:
+    """The tuple batches one lane's mine_many call delivers to its on_batch sink, reduced to a fixed size: exact totals over every
+    tuple, and the DUMP_SAMPLE tuples with the smallest keys, a key being a seeded hash of (lane, position of the tuple in the lane's
+    output order).  The sample depends on the output alone, not on where the batches happen to be cut."""
+
+    def __init__(self, lane):
+        self.lane = lane
+        self.seen = self.pairs = self.letters = self.freq_sum = 0
+        self.rows = None
+
+    def add(self, b):
+        import ctypes as C
+        import numpy as np
+        nt = int(b.ntuples)
+        if nt == 0:
+            return
+        poff = np.ctypeslib.as_array(b.path_off, (nt + 1,)).astype(np.int64)
+        qoff = np.ctypeslib.as_array(b.pair_off, (nt + 1,)).astype(np.int64)
+        nletters, npairs = int(poff[nt]), int(qoff[nt])
+        letters = np.frombuffer((C.c_char * nletters).from_address(b.path_bytes), np.uint8) if nletters else np.zeros(1, np.uint8)
+        ids = np.ctypeslib.as_array(b.ids, (npairs,)) if npairs else np.zeros(1, np.uint32)
+        freqs = np.ctypeslib.as_array(b.freqs, (npairs,)) if npairs else np.zeros(1, np.uint64)
+        self.pairs += npairs
+        self.letters += nletters
+        self.freq_sum += int(freqs[:npairs].sum(dtype=np.uint64))
+        pos = np.arange(self.seen, self.seen + nt, dtype=np.uint64)
+        self.seen += nt
+        keys = _mix64((pos | (np.uint64(self.lane) << np.uint64(48))) ^ np.uint64(DUMP_SEED))
+        if self.rows is not None and len(self.rows["key"]) == DUMP_SAMPLE:
+            sel = np.flatnonzero(keys < self.rows["key"].max())
+        elif nt > DUMP_SAMPLE:
+            sel = np.argpartition(keys, DUMP_SAMPLE - 1)[:DUMP_SAMPLE]
+        else:
+            sel = np.arange(nt)
+        if len(sel) == 0:
+            return
+        # copies of the selected tuples (the batch's arrays are valid during this call only), paths and pairs padded to the widest
+        ps, pn = poff[sel], poff[sel + 1] - poff[sel]
+        col = np.arange(max(1, int(pn.max())))
+        m = col[None, :] < pn[:, None]
+        path = np.zeros(m.shape, np.uint8)
+        path[m] = letters[(ps[:, None] + col[None, :])[m]]
+        qs, qn = qoff[sel], qoff[sel + 1] - qoff[sel]
+        col = np.arange(max(1, int(qn.max())))
+        m = col[None, :] < qn[:, None]
+        j = (qs[:, None] + col[None, :])[m]
+        pid = np.zeros(m.shape, np.uint32)
+        pid[m] = ids[j]
+        pfr = np.zeros(m.shape, np.uint64)
+        pfr[m] = freqs[j]
+        new = {"key": keys[sel], "lane": np.full(len(sel), self.lane, np.int64), "pos": pos[sel].astype(np.int64),
+               "entropy": np.ctypeslib.as_array(b.entropy, (nt,))[sel].copy(), "plen": pn, "path": path, "npair": qn, "ids": pid,
+               "freqs": pfr}
+        self.rows = _cat_rows(self.rows, new)
+        if len(self.rows["key"]) > DUMP_SAMPLE:
+            self.rows = _take(self.rows, np.argpartition(self.rows["key"], DUMP_SAMPLE - 1)[:DUMP_SAMPLE])
+
+
+class StreamSample:
+    """stream mode: the wire streams one lane's enumerate_many call delivers to its on_piece sink -- per prefix the byte count, the
+    CRC-32 of the whole stream and its first DUMP_HEAD bytes"""
+
+    def __init__(self, lane, nprefix):
+        self.lane = lane
+        self.nbytes, self.crc, self.head = [0] * nprefix, [0] * nprefix, [b""] * nprefix
+
+    def add(self, k, piece):
+        import zlib
+        self.nbytes[k] += len(piece)
+        self.crc[k] = zlib.crc32(piece, self.crc[k])
+        if len(self.head[k]) < DUMP_HEAD:
+            self.head[k] += piece[:DUMP_HEAD - len(self.head[k])]
+
+
+def write_dump(d, lanes, nprefix, world, rank):
+    """Writes the captures of the lanes' last timed step as <d>/<name>.npy (<name>_rank<r>.npy when there are several ranks):
+      counts       float64  the step's Stats summed over the lanes: reported (trie nodes), union_nodes, tuples, pairs
+    mining (the tuples metaserver prints, in its order; sample = the tuples of smallest key, fewer when the budget is reached,
+    in (lane, position) order):
+      totals       float64  over EVERY tuple the sinks received: tuples, pairs, path letters, sum of the frequencies
+      tuple_lane, tuple_pos  float64  lane of the tuple and its position in the lane's output of the step
+      entropy      float64  the tuple's entropy
+      path_off, path         float64 offsets (sample size + 1) into float32 ASCII codes of the substrings
+      pair_off, pair_id, pair_freq  float64 offsets into the tuple's id:freq pairs (ids float32, freqs float64)
+    stream mode (prefixes in the order of the run):
+      stream_bytes, stream_crc32  float64  per prefix;  stream_head_off, stream_head  float64 offsets into float32 byte values"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    budget = DUMP_BYTES // world
+    sfx = "_rank%d" % rank if world > 1 else ""
+    files = {}
+    stats = [ln["dump"][1] for ln in lanes]
+    files["counts"] = np.array([sum(float(getattr(s, f)) for s in stats) for f in ("reported", "union_nodes", "tuples", "pairs")], np.float64)
+    caps = [ln["dump"][0] for ln in lanes]
+    if isinstance(caps[0], StreamSample):
+        order = sorted((c.lane + k * len(lanes), c, k) for c in caps for k in range(len(c.nbytes)))  # lane j took prefixes j::nlanes
+        assert len(order) == nprefix
+        files["stream_bytes"] = np.array([c.nbytes[k] for _, c, k in order], np.float64)
+        files["stream_crc32"] = np.array([c.crc[k] for _, c, k in order], np.float64)
+        per = max(0, (budget - 64 * nprefix) // 4 // max(1, nprefix))
+        heads = [np.frombuffer(c.head[k][:per], np.uint8) for _, c, k in order]
+        files["stream_head_off"] = np.concatenate([[0], np.cumsum([len(h) for h in heads])]).astype(np.float64)
+        files["stream_head"] = (np.concatenate(heads) if heads else np.zeros(0, np.uint8)).astype(np.float32)
+    else:
+        files["totals"] = np.array([float(sum(c.seen for c in caps)), float(sum(c.pairs for c in caps)),
+                                    float(sum(c.letters for c in caps)), float(sum(c.freq_sum for c in caps))], np.float64)
+        rows = None
+        for c in caps:
+            if c.rows is not None:
+                rows = _cat_rows(rows, c.rows)
+        if rows is None:  # no tuple at all: empty arrays
+            rows = {"key": np.zeros(0, np.uint64), "lane": np.zeros(0, np.int64), "pos": np.zeros(0, np.int64), "entropy": np.zeros(0),
+                    "plen": np.zeros(0, np.int64), "path": np.zeros((0, 1), np.uint8), "npair": np.zeros(0, np.int64),
+                    "ids": np.zeros((0, 1), np.uint32), "freqs": np.zeros((0, 1), np.uint64)}
+        rows = _take(rows, np.argsort(rows["key"], kind="stable")[:DUMP_SAMPLE])
+        cost = 40 + 4 * rows["plen"] + 12 * rows["npair"]  # bytes a tuple adds to the files
+        keep = int(np.searchsorted(np.cumsum(cost), budget - 4096, side="right"))
+        rows = _take(rows, slice(0, keep))
+        rows = _take(rows, np.lexsort((rows["pos"], rows["lane"])))
+        files["tuple_lane"] = rows["lane"].astype(np.float64)
+        files["tuple_pos"] = rows["pos"].astype(np.float64)
+        files["entropy"] = rows["entropy"].astype(np.float64)
+        pm = np.arange(rows["path"].shape[1])[None, :] < rows["plen"][:, None]
+        files["path_off"] = np.concatenate([[0], np.cumsum(rows["plen"])]).astype(np.float64)
+        files["path"] = rows["path"][pm].astype(np.float32)
+        qm = np.arange(rows["ids"].shape[1])[None, :] < rows["npair"][:, None]
+        files["pair_off"] = np.concatenate([[0], np.cumsum(rows["npair"])]).astype(np.float64)
+        files["pair_id"] = rows["ids"][qm].astype(np.float32)
+        files["pair_freq"] = rows["freqs"][qm].astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(d, name + sfx + ".npy"), a)
+    return sum(a.nbytes for a in files.values())
+
+
 def main():
     args = parse()
     if os.environ.get("DSM_BENCH_WATCHDOG"):  # rehearsal aid: dump every thread's stack if the run stalls
@@ -567,16 +746,21 @@ def main():
         import threading
         tot_lock = threading.Lock()
 
-        def lane_step(lane, record, errs):
+        def lane_step(lane, record, errs, dump=False):
             try:
                 if gate is not None:
                     gate.begin(lanes.index(lane))
                 with torch.cuda.stream(lane["stream"]):
+                    # dump: the sink of this step also hands its output to a capture (what a caller of the path receives)
                     if args.stream_mode:
-                        nbs, st = lane["miner"].enumerate_many(lane["prefixes"], discard=True)
+                        cap = StreamSample(lanes.index(lane), len(lane["prefixes"])) if dump else None
+                        nbs, st = lane["miner"].enumerate_many(lane["prefixes"], discard=True, on_piece=cap.add if dump else None)
                         tot["wire_bytes"] = tot.get("wire_bytes", 0) + (sum(nbs) if record else 0)
                     else:
-                        st = lane["miner"].mine_many(lane["prefixes"], text=False)[1]
+                        cap = TupleSample(lanes.index(lane)) if dump else None
+                        st = lane["miner"].mine_many(lane["prefixes"], text=False, on_batch=cap.add if dump else None)[1]
+                    if dump:
+                        lane["dump"] = (cap, st)
                 if record:
                     with tot_lock:
                         tot["reported"] += st.reported
@@ -610,14 +794,14 @@ def main():
                 if gate is not None:
                     gate.retire(lanes.index(lane))
 
-        def step(record):
+        def step(record, dump=False):
             errs = []
             if gate is not None:
                 gate.reset()
             if len(lanes) == 1:
-                lane_step(lanes[0], record, errs)
+                lane_step(lanes[0], record, errs, dump)
             else:
-                ths = [threading.Thread(target=lane_step, args=(ln, record, errs)) for ln in lanes]
+                ths = [threading.Thread(target=lane_step, args=(ln, record, errs, dump)) for ln in lanes]
                 for t in ths:
                     t.start()
                 for t in ths:
@@ -648,8 +832,8 @@ def main():
             step(False)
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step(True)
+        for i in range(args.steps):
+            step(True, dump=args.dump_outputs is not None and i == args.steps - 1)
         barrier()
         dt = time.perf_counter() - t0
         t = torch.tensor([dt, float(tot["reported"])], dtype=torch.float64, device=dev if dist.is_initialized() and dist.get_backend() == "nccl" else "cpu")
@@ -688,6 +872,9 @@ def main():
         open_lanes = res["lanes"]
     owner_mode, plen, prefixes, pmin, nlanes, lanes, native = (res[k] for k in ("owner_mode", "plen", "prefixes", "pmin", "nlanes", "lanes", "native"))
     tot, dt, reported_all = res["tot"], res["dt"], res["reported_all"]
+    if args.dump_outputs is not None:
+        nb = write_dump(args.dump_outputs, lanes, len(prefixes), world, rank)
+        print("bench: rank %d wrote %.1f MB of outputs to %s" % (rank, nb / 1e6, args.dump_outputs), file=sys.stderr, flush=True)
     # Text (metaserver.cpp:472-484's printf loop) is outside the timed region of `value` (the sink receives binary batches).  One more
     # pass with a sink that formats every batch on the GPU (dsm_formatter_format, the drop-in's way since round 4), timed twice: the
     # calls alone (`format_ms_per_step`) and the whole pass (`text_pass_ms`: what a user of the text surface waits for; the formatter's

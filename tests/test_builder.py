@@ -88,7 +88,7 @@ def test_reference_client_reads_our_file(golden, builder, tmp_path):
             buf.append(b)
         got.append(b"".join(buf))
 
-    t = threading.Thread(target=sink)
+    t = threading.Thread(target=sink, daemon=True)  # (a client that fails before it connects must not keep the session from exiting)
     t.start()
     subprocess.run([os.path.join(REF, "metaenumerate"), "--fmin", "2", out], input=("127.0.0.1 %d GT\n" % srv.getsockname()[1]).encode(),
                    check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)

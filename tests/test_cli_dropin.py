@@ -119,11 +119,16 @@ def test_patched_reference_client_sends_the_reference_streams(golden):
             s.close()
             got[p] = buf
 
-        ths = [threading.Thread(target=serve, args=ps) for ps in socks]
+        # (daemon: a client that never connects must fail this test, not keep the session from exiting)
+        ths = [threading.Thread(target=serve, args=ps, daemon=True) for ps in socks]
         for t in ths:
             t.start()
+        # the library of this tree, whichever checkout the prebuilt oracle/_ref binary was linked in (LD_LIBRARY_PATH goes before
+        # its RUNPATH)
+        env = dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(filter(None, [os.path.join(ROOT, "dsm-framework_amd"),
+                                                                             os.environ.get("LD_LIBRARY_PATH")])))
         r = subprocess.run([os.path.join(REF, "metaenumerate_patched"), "--fmin", "2", golden.fmi("toy3", name)], input=hosts.encode(),
-                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300, env=env)
         for t in ths:
             t.join(timeout=60)
         assert r.returncode == 0, r.stderr
