@@ -4,6 +4,7 @@ Host-side mirror of the reference's interfaces for the substring-enumeration pat
   Index            ~ TextCollection::load / FMIndex (LF, getL, getLength)      FMIndex.h:68-102
   Index.enumerate  ~ EnumerateQuery::enumerate + ClientSocket encoders         EnumerateQuery.cpp:9-290
   mine             ~ all clients + metaserver traverse() for one prefix        metaserver.cpp:269-486
+  Counter / count  ~ FMIndex::Search over many patterns and samples            FMIndex.cpp:360-382
 There is no CPU fallback: every call runs HIP kernels and raises DsmError when the library or a GPU is missing.
 """
 import ctypes as C
@@ -40,6 +41,17 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class CountStats(C.Structure):
+    _fields_ = [("patterns", C.c_uint64), ("items", C.c_uint64), ("lf_steps", C.c_uint64), ("block_loads", C.c_uint64),
+                ("wave_steps", C.c_uint64), ("lane_steps", C.c_uint64), ("table_starts", C.c_uint64), ("rare_blocks", C.c_uint64),
+                ("kmer", C.c_uint32), ("reserved", C.c_uint32), ("table_bytes", C.c_uint64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+        d["lane_efficiency"] = self.lane_steps / (64.0 * self.wave_steps) if self.wave_steps else None
+        return d
 
 
 class TupleBatch(C.Structure):
@@ -164,6 +176,12 @@ def lib():
         L.dsm_distmat_add_text.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
         L.dsm_distmat_finish.argtypes = [C.c_void_p] + [C.c_void_p] * 6
         L.dsm_distmat_format.argtypes = [C.c_uint32, C.c_uint32] + [C.c_void_p] * 6 + [C.POINTER(C.c_void_p)]
+        L.dsm_counter_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.dsm_counter_count.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.dsm_counter_count_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.dsm_counter_stats.argtypes = [C.c_void_p, C.POINTER(CountStats), C.c_int]
+        L.dsm_counter_destroy.argtypes = [C.c_void_p]
+        L.dsm_counter_destroy.restype = None
         _lib = L
     return _lib
 
@@ -625,6 +643,70 @@ def mine(indexes, prefix, fmin=10, maxdepth=MAXDEPTH_NONE, pmin=2, pmax=0, minde
     finally:
         _close_sink(cb)
     return (b"".join(out) if text else None), st
+
+
+def pack_patterns(patterns):
+    """list of str / bytes -> (bytes as uint8 array, offsets[npat + 1] as uint64 array); str is encoded as latin-1 (one byte per char)"""
+    bs = [p if isinstance(p, (bytes, bytearray)) else p.encode("latin-1") for p in patterns]
+    off = np.zeros(len(bs) + 1, np.uint64)
+    if bs:
+        np.cumsum([len(b) for b in bs], out=off[1:])
+    data = np.frombuffer(b"".join(bs), np.uint8) if bs else np.zeros(0, np.uint8)
+    return data, off
+
+
+class Counter:
+    """Occurrence counts of patterns in every index (dsm_counter_*): FMIndex::Search, batched on the GPU.
+
+    kmer=None: the library's default k-mer table (10); 0: no table.  .count(patterns) -> uint64 array [npat, nidx]
+    (with_sp=True: also the start of each final interval, unspecified where the count is 0)."""
+
+    def __init__(self, indexes, kmer=None):
+        self.indexes = list(indexes)
+        hs = (C.c_void_p * len(self.indexes))(*[ix.h for ix in self.indexes])
+        self.h = C.c_void_p()
+        _check(lib().dsm_counter_create(hs, len(self.indexes), -1 if kmer is None else int(kmer), C.byref(self.h)))
+
+    def count(self, patterns, with_sp=False):
+        data, off = pack_patterns(patterns)
+        return self.count_packed(data, off, with_sp)
+
+    def count_packed(self, data, off, with_sp=False):
+        """the same on packed input: data uint8[...], off uint64[npat + 1]"""
+        data = np.ascontiguousarray(data, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        npat = len(off) - 1
+        cnt = np.zeros((npat, len(self.indexes)), np.uint64)
+        sp = np.zeros((npat, len(self.indexes)), np.uint64) if with_sp else None
+        _check(lib().dsm_counter_count(self.h, data.ctypes.data if len(data) else None, off.ctypes.data, npat, cnt.ctypes.data,
+                                       sp.ctypes.data if with_sp else None))
+        return (cnt, sp) if with_sp else cnt
+
+    def count_dev(self, d_bytes, d_offsets, npat, d_counts, d_sp=None, stream=None):
+        """device pointers (ints), enqueued on `stream` without synchronisation"""
+        _check(lib().dsm_counter_count_dev(self.h, d_bytes, d_offsets, npat, d_counts, d_sp, stream))
+
+    def stats(self, reset=False):
+        st = CountStats()
+        _check(lib().dsm_counter_stats(self.h, C.byref(st), 1 if reset else 0))
+        return st
+
+    def close(self):
+        if self.h:
+            lib().dsm_counter_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def count(indexes, patterns, kmer=None, with_sp=False):
+    """One-shot Counter(indexes, kmer).count(patterns)."""
+    with Counter(indexes, kmer) as c:
+        return c.count(patterns, with_sp)
 
 
 class Trie:

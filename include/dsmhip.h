@@ -336,6 +336,45 @@ void dsm_formatter_destroy(dsm_formatter* f);
 int dsm_format_batch_dev(const dsm_tuple_batch* batch, int device, char** text, size_t* len);
 
 /* ------------------------------------------------------------------------------------------------
+ * Occurrence counts of given patterns in every sample: FMIndex::Search (FMIndex.cpp:360-382), batched.
+ *   A pattern is a byte string in READ orientation.  Its count in a sample is the size of the interval reached by pushing its bytes
+ *   left to right from the root [0, n-1], each push sp' = LF(c, sp-1), ep' = LF(c, ep) - 1 (Query.h:37-45): FMIndex::Search on the
+ *   reversed pattern, i.e. the occurrences over the reads and their reverse complements -- the `freq` of the server's tuples.
+ *   Bytes are taken as given (no case folding, no N normalisation): a byte the index does not contain gives 0; the index's own
+ *   non-base symbols ('\0', '-', 'N') are counted exactly.  The empty pattern gives n.  The search stops once the interval is
+ *   empty (count 0).  sp (optional): the start of the final interval; unspecified where the count is 0.
+ * A counter holds indexes of ONE device (DSM_E_INVAL otherwise, and for an offloaded index) and, unless kmer = 0, one table per
+ * index of (sp, count) for every ACGT string of length 1..kmer (kmer = -1: 10, 22 MB per index; at most 12), built on the device
+ * by dsm_counter_create; a pattern whose first min(kmer, len) bytes are bases starts from it.  The tables belong to the counter:
+ * dsm_index_device_bytes does not change.  The indexes must stay open (and resident) while the counter is used.
+ * offsets[npat + 1]: pattern p is bytes[offsets[p], offsets[p+1]).  counts and sp: [npat][nidx], sample i at column i.
+ * dsm_counter_count: host pointers, synchronous, any batch size (chunked internally).
+ * dsm_counter_count_dev: device pointers, enqueued on `stream`, no synchronisation.
+ * dsm_counter_stats: work since creation or the last reset (synchronises the device first); lane efficiency = lane_steps /
+ * (wave_steps * 64).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct dsm_counter dsm_counter;
+typedef struct dsm_count_stats {
+    uint64_t patterns;      /* patterns counted */
+    uint64_t items;         /* (pattern, sample) pairs */
+    uint64_t lf_steps;      /* pushes taken by the kernel (the table's steps not included) */
+    uint64_t block_loads;   /* 64-byte block loads of those steps (1 when sp and ep+1 share a block, else 2) */
+    uint64_t wave_steps;    /* steps of the kernel's step loop, per wave */
+    uint64_t lane_steps;    /* lanes active in those steps */
+    uint64_t table_starts;  /* items started from the k-mer table */
+    uint64_t rare_blocks;   /* blocks scanned by ranks of the non-base symbols */
+    uint32_t kmer;          /* the counter's table length (0 = no table) */
+    uint32_t reserved;
+    uint64_t table_bytes;   /* HBM held by the tables */
+} dsm_count_stats;
+int dsm_counter_create(dsm_index* const* idx, int nidx, int kmer, dsm_counter** out);
+int dsm_counter_count(dsm_counter* c, const uint8_t* bytes, const uint64_t* offsets, size_t npat, uint64_t* counts, uint64_t* sp);
+int dsm_counter_count_dev(dsm_counter* c, const uint8_t* d_bytes, const uint64_t* d_offsets, size_t npat, uint64_t* d_counts,
+                          uint64_t* d_sp, void* stream);
+int dsm_counter_stats(dsm_counter* c, dsm_count_stats* out, int reset);
+void dsm_counter_destroy(dsm_counter* c);
+
+/* ------------------------------------------------------------------------------------------------
  * Index construction: the multi-string BWT the reference builder computes with incbwt
  * (builder.cpp:183-285, TextCollectionBuilder.cpp:65-152, incbwt/rlcsa_builder.cpp:35-78,165-179).  d_text: n bytes on the
  * device, the strings one after the other, each ending in a 0 byte; string k's terminator sorts as $_k with
