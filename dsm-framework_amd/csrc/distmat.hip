@@ -22,27 +22,71 @@ int fail(int code, const std::string& m);  // index.hip
 constexpr int DM_THREADS = 256;
 constexpr u32 DM_LDS_CELLS = 1024;  // cells (count u32 + three 128-bit sums = 52 B) kept in LDS per block: 52 KB
 
-// The three sums of squared distances are kept as 128-bit fixed-point numbers (64 integer bits, 64 fraction bits, two's complement)
-// and added with integer atomics: integer addition is associative, so a cell's sum does not depend on the order in which lanes,
-// blocks or batches reach it -- the matrices are the same from run to run (round 4; round 3 added doubles in whatever order the
-// atomics arrived, and the last printed digit could differ).  A term is a double; its bits below 2^-64 are dropped (the terms are
-// squares of differences of logs and roots of frequencies, and lgamma values: magnitudes between 1e-10 and 1e12), the sum itself
-// is exact, and it is rounded to a double once, at the end.
+// The three sums of squared distances are kept as fixed-point numbers with 64 fraction bits, two's complement, and added with
+// integer atomics: integer addition is associative, so a cell's sum does not depend on the order in which lanes, blocks or batches
+// reach it -- the matrices are the same from run to run (round 4; round 3 added doubles in whatever order the atomics arrived, and
+// the last printed digit could differ).  A term is a double; its bits below 2^-64 are dropped (the terms are squares of differences
+// of logs and roots of frequencies, and lgamma values: magnitudes between 1e-10 and 1e12), the sum itself is exact, and it is
+// rounded to a double once, at the end.
+// A block's LDS partial is 128 bits (lo, hi): it holds fewer than 2^32 terms of |x| < 2^63, so it fits as a signed number.  The
+// global sum has a third word, top, that takes the sign extension and the carries out of hi: 192 bits hold any sum of fewer than
+// 2^64 such terms, and dsm_distmat_finish refuses a sum that does not fit the 64 integer bits of (hi, lo).  A term that is not finite,
+// or whose magnitude is 2^63 or more, is not added: it sets a bit in the cell's flags, and finish returns the value the tool's IEEE
+// summation gives (NaN, +inf or -inf) or, for a finite out-of-range term, refuses the sum.
 struct Fix128 { unsigned long long lo, hi; };
-__device__ __forceinline__ void fix_add(Fix128* cell, double x) {
-    const double fl = floor(x);
-    const unsigned long long hi = (unsigned long long)(long long)fl;               // (two's complement of a negative integer part)
-    const unsigned long long lo = __double2ull_rz((x - fl) * 18446744073709551616.0);  // the fraction, in [0, 1), scaled by 2^64
-    const unsigned long long old = atomicAdd(&cell->lo, lo);
-    atomicAdd(&cell->hi, hi + ((old + lo) < old ? 1ull : 0ull));                    // carries commute with everything else
+struct FixCell { unsigned long long lo, hi, top; unsigned flags, pad; };
+constexpr unsigned FX_PINF = 1, FX_NINF = 2, FX_NAN = 4, FX_RANGE = 8;
+constexpr double TWO63 = 9223372036854775808.0, TWO64 = 18446744073709551616.0;
+
+// adds a 128-bit addend to (lo, hi); returns the carry out of hi (0, 1 or 2)
+__device__ __forceinline__ unsigned long long fix_add_words(unsigned long long* lo, unsigned long long* hi, unsigned long long alo,
+                                                           unsigned long long ahi) {
+    const unsigned long long old = atomicAdd(lo, alo);
+    const unsigned long long h = ahi + ((old + alo) < old ? 1ull : 0ull);    // carries commute with everything else
+    unsigned long long c = h < ahi ? 1ull : 0ull;
+    if (h) {
+        const unsigned long long oh = atomicAdd(hi, h);
+        c += (oh + h) < oh ? 1ull : 0ull;
+    }
+    return c;
 }
-__device__ __forceinline__ void fix_merge(Fix128* cell, const Fix128& v) {
-    if (!v.lo && !v.hi) return;
-    const unsigned long long old = atomicAdd(&cell->lo, v.lo);
-    atomicAdd(&cell->hi, v.hi + ((old + v.lo) < old ? 1ull : 0ull));
+// a signed 128-bit addend into a 192-bit global sum
+__device__ __forceinline__ void fix_add_signed(FixCell* cell, unsigned long long alo, unsigned long long ahi) {
+    const unsigned long long t = ((long long)ahi < 0 ? ~0ull : 0ull) + fix_add_words(&cell->lo, &cell->hi, alo, ahi);
+    if (t) atomicAdd(&cell->top, t);
 }
-static inline double fix_to_double(const Fix128& v) {   // (host) hi is signed, lo the fraction
-    return (double)(long long)v.hi + (double)v.lo * (1.0 / 18446744073709551616.0);
+// x as a 128-bit addend; false (and a flag bit set in *flags) when x is not finite or |x| >= 2^63
+__device__ __forceinline__ bool fix_split(double x, unsigned long long& lo, unsigned long long& hi, unsigned* flags) {
+    if (!(fabs(x) < TWO63)) {
+        atomicOr(flags, x != x ? FX_NAN : x == INFINITY ? FX_PINF : x == -INFINITY ? FX_NINF : FX_RANGE);
+        return false;
+    }
+    double fl = floor(x), fr = (x - fl) * TWO64;
+    if (fr >= TWO64) { fl += 1.0; fr = 0.0; }  // x - fl rounded to 1.0 (x negative and tiny): the term is 0 to within 2^-64
+    hi = (unsigned long long)(long long)fl;    // (two's complement of a negative integer part)
+    lo = __double2ull_rz(fr);                  // the fraction, in [0, 1), scaled by 2^64
+    return true;
+}
+__device__ __forceinline__ void fix_add(FixCell* cell, double x) {
+    unsigned long long lo, hi;
+    if (fix_split(x, lo, hi, &cell->flags)) fix_add_signed(cell, lo, hi);
+}
+__device__ __forceinline__ void fix_add_lds(Fix128* l, FixCell* cell, double x) {
+    unsigned long long lo, hi;
+    if (fix_split(x, lo, hi, &cell->flags)) (void)fix_add_words(&l->lo, &l->hi, lo, hi);
+}
+__device__ __forceinline__ void fix_merge(FixCell* cell, const Fix128& v) {
+    if (v.lo || v.hi) fix_add_signed(cell, v.lo, v.hi);
+}
+// (host) the sum rounded to a double once; false when it does not fit the fixed-point range
+static inline bool fix_to_double(const FixCell& v, double* out) {
+    const bool pinf = v.flags & FX_PINF, ninf = v.flags & FX_NINF;
+    if ((v.flags & FX_NAN) || (pinf && ninf)) { *out = std::copysign(NAN, -1.0); return true; }  // x86's default NaN, "-nan" in %f
+    if (pinf || ninf) { *out = pinf ? INFINITY : -INFINITY; return true; }
+    if ((v.flags & FX_RANGE) || v.top != ((long long)v.hi < 0 ? ~0ull : 0ull)) return false;
+    const __int128 q = (__int128)(((unsigned __int128)v.hi << 64) | v.lo);
+    *out = (double)q * (1.0 / TWO64);  // one rounding: the conversion; the scaling by 2^-64 is exact
+    return true;
 }
 
 struct DmArgs {
@@ -57,9 +101,9 @@ struct DmArgs {
     const u32* freqs;
     const signed char* bucket;  // per tuple, -1 = none
     u32* count;        // [nm][s][s]
-    Fix128* mlog;
-    Fix128* msqrt;
-    Fix128* mlgamma;
+    FixCell* mlog;
+    FixCell* msqrt;
+    FixCell* mlgamma;
     const double* nfactor;  // -N: 1 / dataset size per sample (null: raw frequencies)
 };
 
@@ -112,9 +156,10 @@ __global__ __launch_bounds__(DM_THREADS) void distmat_kernel(DmArgs a) {
         __syncthreads();
         if (b >= 0) {
             const size_t base = (size_t)b * a.s * a.s;
-            if (lane < a.s && pr[lane]) {  // diagonal count, add() :170-172 with j == k
-                if (a.use_lds) atomicAdd(&l_cnt[base + (size_t)lane * a.s + lane], 1u);
-                else atomicAdd(&a.count[base + (size_t)lane * a.s + lane], 1u);
+            for (u32 x = lane; x < a.s; x += a.G) {  // diagonal count, add() :170-172 with j == k
+                if (!pr[x]) continue;
+                if (a.use_lds) atomicAdd(&l_cnt[base + (size_t)x * a.s + x], 1u);
+                else atomicAdd(&a.count[base + (size_t)x * a.s + x], 1u);
             }
             for (u32 p = lane; p < a.npairs; p += a.G) {
                 u32 j = pj, k = pk;
@@ -131,12 +176,17 @@ __global__ __launch_bounds__(DM_THREADS) void distmat_kernel(DmArgs a) {
                         const double xj = (double)fj * a.nfactor[j], xk = (double)fk * a.nfactor[k];
                         dl = log(xj + 1.0) - log(xk + 1.0);
                         ds = sqrt(xj) - sqrt(xk);
-                    } else {
-                        dl = log((double)fj + 1.0) - log((double)fk + 1.0);
+                    } else {  // the tool's unsigned sums: 1 + freq and freq[j] + freq[k] + 1 wrap modulo 2^32 (add() :183-188)
+                        const u32 sj = fj + 1u, sk = fk + 1u, sjk = fj + fk + 1u;
+                        dl = log((double)sj) - log((double)sk);
                         ds = sqrt((double)fj) - sqrt((double)fk);
-                        lg = lgamma((double)fj + (double)fk + 1.0) - lgamma((double)fj + 1.0) - lgamma((double)fk + 1.0) - ((double)fj + (double)fk + 1.0);
+                        lg = lgamma((double)sjk) - lgamma((double)sj) - lgamma((double)sk) - (double)sjk;
                     }
-                    if (a.use_lds) { fix_add(&l_log[cell], dl * dl); fix_add(&l_sqrt[cell], ds * ds); if (!a.nfactor) fix_add(&l_lgam[cell], lg); }
+                    if (a.use_lds) {
+                        fix_add_lds(&l_log[cell], &a.mlog[cell], dl * dl);
+                        fix_add_lds(&l_sqrt[cell], &a.msqrt[cell], ds * ds);
+                        if (!a.nfactor) fix_add_lds(&l_lgam[cell], &a.mlgamma[cell], lg);
+                    }
                     else { fix_add(&a.mlog[cell], dl * dl); fix_add(&a.msqrt[cell], ds * ds); if (!a.nfactor) fix_add(&a.mlgamma[cell], lg); }
                 }
             }
@@ -167,7 +217,7 @@ struct dsm_distmat {
     std::vector<double> nfactor;      // -N: 1 / size
     double* d_nfactor = nullptr;
     u32* d_count = nullptr;
-    dsm::Fix128 *d_log = nullptr, *d_sqrt = nullptr, *d_lgamma = nullptr;  // 128-bit fixed-point sums (see Fix128)
+    dsm::FixCell *d_log = nullptr, *d_sqrt = nullptr, *d_lgamma = nullptr;  // fixed-point sums (see Fix128)
     // upload staging (grown on demand)
     void *d_pair_off = nullptr, *d_ids = nullptr, *d_freqs = nullptr, *d_bucket = nullptr;
     size_t cap_t = 0, cap_p = 0;
@@ -229,8 +279,9 @@ int dsm_distmat_create_ex(int device, uint32_t samples, const double* maxent, ui
         for (u32 i = 0; i < samples; ++i) m->nfactor[i] = (double)1 / sizes[i];
     }
     const size_t cells = (size_t)nmaxent * samples * samples;
-    if (hipMalloc(&m->d_count, cells * 4) != hipSuccess || hipMalloc(&m->d_log, cells * 16) != hipSuccess ||
-        hipMalloc(&m->d_sqrt, cells * 16) != hipSuccess || hipMalloc(&m->d_lgamma, cells * 16) != hipSuccess) {
+    const size_t fb = cells * sizeof(FixCell);
+    if (hipMalloc(&m->d_count, cells * 4) != hipSuccess || hipMalloc(&m->d_log, fb) != hipSuccess ||
+        hipMalloc(&m->d_sqrt, fb) != hipSuccess || hipMalloc(&m->d_lgamma, fb) != hipSuccess) {
         dsm_distmat_destroy(m);
         return fail(DSM_E_NOMEM, "hipMalloc failed");
     }
@@ -238,8 +289,8 @@ int dsm_distmat_create_ex(int device, uint32_t samples, const double* maxent, ui
         if (hipMalloc(&m->d_nfactor, samples * 8) != hipSuccess) { dsm_distmat_destroy(m); return fail(DSM_E_NOMEM, "hipMalloc failed"); }
         (void)hipMemcpy(m->d_nfactor, m->nfactor.data(), samples * 8, hipMemcpyHostToDevice);
     }
-    (void)hipMemset(m->d_count, 0, cells * 4); (void)hipMemset(m->d_log, 0, cells * 16);
-    (void)hipMemset(m->d_sqrt, 0, cells * 16); (void)hipMemset(m->d_lgamma, 0, cells * 16);
+    (void)hipMemset(m->d_count, 0, cells * 4); (void)hipMemset(m->d_log, 0, fb);
+    (void)hipMemset(m->d_sqrt, 0, fb); (void)hipMemset(m->d_lgamma, 0, fb);
     *out = m;
     return DSM_OK;
 }
@@ -443,13 +494,18 @@ int dsm_distmat_finish(dsm_distmat* m, double* maxent_sorted, uint32_t* noutput,
     std::vector<double> l(cells), q(cells), g(cells);
     DM_HIP(hipMemcpy(c.data(), m->d_count, cells * 4, hipMemcpyDeviceToHost));
     {
-        std::vector<Fix128> f(cells);
-        DM_HIP(hipMemcpy(f.data(), m->d_log, cells * 16, hipMemcpyDeviceToHost));
-        for (size_t x = 0; x < cells; ++x) l[x] = fix_to_double(f[x]);
-        DM_HIP(hipMemcpy(f.data(), m->d_sqrt, cells * 16, hipMemcpyDeviceToHost));
-        for (size_t x = 0; x < cells; ++x) q[x] = fix_to_double(f[x]);
-        DM_HIP(hipMemcpy(f.data(), m->d_lgamma, cells * 16, hipMemcpyDeviceToHost));
-        for (size_t x = 0; x < cells; ++x) g[x] = fix_to_double(f[x]);
+        std::vector<FixCell> f(cells);
+        const FixCell* src[3] = {m->d_log, m->d_sqrt, m->d_lgamma};
+        std::vector<double>* dst[3] = {&l, &q, &g};
+        static const char* name[3] = {"log", "sqrt", "lgamma"};
+        for (int k = 0; k < 3; ++k) {
+            DM_HIP(hipMemcpy(f.data(), src[k], cells * sizeof(FixCell), hipMemcpyDeviceToHost));
+            for (size_t x = 0; x < cells; ++x)
+                if (!fix_to_double(f[x], &(*dst[k])[x]))
+                    return fail(DSM_E_UNSUPPORTED, std::string("dsm_distmat_finish: the ") + name[k] + " sum of bucket " + std::to_string(x / per) +
+                                                       ", samples " + std::to_string(x % per / m->s) + " and " + std::to_string(x % m->s) +
+                                                       ", has a magnitude of 2^63 or more: outside the fixed-point range");
+        }
     }
     std::vector<u32> nout = m->noutput;
     for (u32 i = m->nm; i > 1;) {  // accumulate(i -> i-1), smtxt2entropy.c:230-242, in the print loop's order (:746-750)

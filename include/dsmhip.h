@@ -425,7 +425,8 @@ int dsm_distmat_add(dsm_distmat* m, const dsm_tuple_batch* batch);
 /* metaserver output lines "path entropy id:freq ...\n" (smtxt2entropy.c:84-125,656-680) */
 int dsm_distmat_add_text(dsm_distmat* m, const char* text, size_t len);
 /* maxent_sorted[nmaxent] (descending, the tool's matrix order), noutput[nmaxent], and four [nmaxent][samples][samples]
- * arrays; any pointer may be NULL.  May be called once. */
+ * arrays; any pointer may be NULL.  May be called once.  A cell with a NaN or infinite term holds what the tool's double sum
+ * holds (-nan, inf or -inf); a sum with a finite term or total of magnitude 2^63 or more is refused (DSM_E_UNSUPPORTED). */
 int dsm_distmat_finish(dsm_distmat* m, double* maxent_sorted, uint32_t* noutput, uint32_t* count, double* mlog, double* msqrt,
                        double* mlgamma);
 /* the tool's four output files (count, log, sqrt, lgamma) as text; each malloc'd, release with dsm_free */

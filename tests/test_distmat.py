@@ -5,8 +5,10 @@ within 1e-9 relative (the GPU adds the same terms in a different order; the tool
 import ctypes as C
 import gzip
 import json
+import math
 import os
 import subprocess
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -36,8 +38,11 @@ def _olib():
 
 def case_input(setname, case):
     info = MAN["distmat"][setname][case]
-    text = b"".join(gzip.open(os.path.join(GOLD, setname, "server.%s.%s.txt.gz" % (info["server_cfg"], p)), "rb").read()
-                    for p in info["prefixes"])
+    if "input" in info:   # synthetic lines (make_golden_distmat.py SYNTH_CASES)
+        text = gzip.open(os.path.join(GOLD, setname, info["input"]), "rb").read()
+    else:
+        text = b"".join(gzip.open(os.path.join(GOLD, setname, "server.%s.%s.txt.gz" % (info["server_cfg"], p)), "rb").read()
+                        for p in info["prefixes"])
     args = info["args"]
     minfreq = int(args[args.index("-M") + 1]) if "-M" in args else 0
     if "-m" in args:
@@ -47,7 +52,7 @@ def case_input(setname, case):
         n = _olib().orc_distmat_steps(float(args[args.index("-e") + 1]), buf, 256)
         maxent = list(buf[:n])
     mapping, sizes = info.get("mapping"), info.get("sizes")
-    smpls = max(mapping) + 1 if mapping else len(MAN["sets"][setname]["names"])
+    smpls = info["samples"] if "samples" in info else max(mapping) + 1 if mapping else len(MAN["sets"][setname]["names"])
     return text, smpls, maxent, minfreq, mapping, sizes
 
 
@@ -96,7 +101,10 @@ def _cmp(res, nout, cnt, mats):
     assert (res["count"] == cnt).all()
     for k, want in zip(("log", "sqrt", "lgamma"), mats):
         got = res[k]
-        assert np.allclose(got, want, rtol=1e-9, atol=1e-6), (k, np.abs(got - want).max())
+        fin = np.isfinite(want)     # the tool's inf and -nan cells: the same value, the sign of a NaN included
+        assert np.array_equal(np.isfinite(got), fin) and np.array_equal(np.isnan(got), np.isnan(want)), k
+        assert np.array_equal(np.signbit(got[~fin]), np.signbit(want[~fin])), k
+        assert np.allclose(got[fin], want[fin], rtol=1e-9, atol=1e-6), (k, np.abs(got[fin] - want[fin]).max())
 
 
 @pytest.mark.gpu
@@ -118,8 +126,7 @@ def test_gpu_distmat_matches_oracle_on_goldens(setname, case, pydsm_mod):
             if b > a:
                 dm.add_text(text[a:b])
         res2 = dm.finish()
-    for k in ("count", "log", "sqrt", "lgamma"):
-        assert np.array_equal(res[k], res2[k]), k
+    _same_bits(res, res2)                 # (NaN cells included)
     got = pydsm_mod.DistMat.format(res)
     assert got[0] == texts[0]             # the count file is exact
     for g, w in zip(got[1:], texts[1:]):  # the double files agree line for line up to the last printed digits
@@ -219,3 +226,302 @@ def test_cli_samplefile_and_normalize(tmp_path):
                     assert abs(float(a) - float(b)) <= 1e-9 * max(1.0, abs(float(b))) + 2e-6, (kind, a, b)
     r = subprocess.run([exe, "-s", "3", "-S", "map.txt", "-m", "1.0", "-F", "x"], input=text, cwd=tmp_path, capture_output=True)
     assert r.returncode == 1
+
+
+def _gpu_run(pydsm, text, smpls, maxent, minfreq=0, mapping=None, sizes=None, pieces=1):
+    """dsm_distmat on the lines of text, cut into `pieces` batches at line ends."""
+    with pydsm.DistMat(smpls, maxent=maxent, minfreq=minfreq, run_to_sample=mapping, sizes=sizes) as dm:
+        cuts = [0] + [text.rfind(b"\n", 0, len(text) * k // pieces) + 1 for k in range(1, pieces)] + [len(text)]
+        for a, b in zip(cuts, cuts[1:]):
+            if b > a:
+                dm.add_text(text[a:b])
+        return dm.finish()
+
+
+def _same_bits(r1, r2):
+    for k in ("noutput", "count", "log", "sqrt", "lgamma"):
+        assert r1[k].tobytes() == r2[k].tobytes(), k
+
+
+def _random_lines(rng, runs, n, maxk, big=0.05, wrap=0.0, dup=0.0):
+    """Server lines with random ids, frequencies mostly below 400 (zeros included), a share >= 1e5, lines with two
+    frequencies >= 2^31 (wrap) and repeated ids (dup)."""
+    out = []
+    for _ in range(n):
+        k = int(rng.integers(1, maxk + 1))
+        ids = rng.choice(runs, k, replace=False).tolist()
+        fr = np.where(rng.random(k) < big, rng.integers(100000, 3000000, k), rng.integers(0, 400, k)).tolist()
+        if k >= 2 and rng.random() < wrap:
+            fr[0], fr[1] = rng.integers(2 ** 31, 2 ** 32 - 1, 2).tolist()
+        if rng.random() < dup:
+            ids.append(ids[0])
+            fr.append(int(rng.integers(0, 400)))
+        out.append("GATTACA 0.5 " + " ".join("%d:%d" % p for p in zip(ids, fr)) + "\n")
+    return "".join(out).encode()
+
+
+# (samples, buckets, mode, lines): every sample count on both sides of the 64 lanes of a tuple group and of the 2 * 32 pair
+# limit, buckets on both sides of the 1024 cells that go to LDS, the plain mode, -N (one case with a negative size: -nan cells)
+# and -S.  s = 4 with 70000 lines: G = 8, 2048 blocks of 32 groups, so the grid-stride loop runs twice (and the host pass
+# runs in several threads).
+SWEEP = [(2, 1, "plain", 3000), (3, 3, "S", 3000), (4, 2, "plain", 70000), (8, 16, "plain", 20000), (8, 17, "N", 3000),
+         (11, 8, "N", 3000), (12, 7, "plain", 3000), (12, 8, "S", 3000), (18, 3, "S", 2000), (19, 3, "plain", 2000),
+         (32, 1, "plain", 2000), (33, 1, "N", 2000), (63, 2, "S", 1000), (64, 1, "plain", 1000), (65, 2, "Nneg", 1000),
+         (70, 3, "plain", 1000), (128, 2, "S", 500), (219, 2, "plain", 300), (273, 1, "N", 200)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("s,nm,mode,n", SWEEP, ids=["s%d_nm%d_%s" % c[:3] for c in SWEEP])
+def test_gpu_distmat_sample_and_bucket_sweep(s, nm, mode, n, pydsm_mod):
+    rng = np.random.default_rng(1000 * s + nm)
+    mapping = sizes = None
+    runs = s
+    if mode == "S":
+        runs = s + s // 2 + 1
+        mapping = rng.permutation(np.concatenate([np.arange(s), rng.integers(0, s, runs - s)])).tolist()
+    if mode.startswith("N"):
+        sizes = (2.0 ** rng.integers(-3, 8, s) * rng.choice([1.0, 1.5, 3.0], s)).tolist()
+        if mode == "Nneg":
+            sizes[s // 3] = -1e6
+    maxent = sorted(rng.uniform(0.2, 0.95, nm - 1).tolist()) + [1.0]
+    minfreq = 3 if s % 2 else 0
+    text = _random_lines(rng, runs, n, min(runs, 120), wrap=0.05 if mode == "plain" else 0.0, dup=0.1)
+    texts, nout, cnt, mats = oracle_run(text, s, maxent, minfreq, mapping, sizes)
+    res = _gpu_run(pydsm_mod, text, s, maxent, minfreq, mapping, sizes)
+    _cmp(res, nout, cnt, mats)
+    assert np.diagonal(res["count"][0]).min() > 0 or s > 100     # every sample occurs: the diagonal is not trivially 0
+    if mode == "Nneg":
+        assert np.isnan(mats[1]).any()
+    _same_bits(res, _gpu_run(pydsm_mod, text, s, maxent, minfreq, mapping, sizes, pieces=5))
+
+
+def _bucket_of(freqs, s, maxent, nfactor=None):
+    """Bucket of one tuple ({sample: freq}, duplicates resolved) as smtxt2entropy.c:128-165, 690-703 pick it; also returns the
+    distance of the entropy to the nearest bound."""
+    L2 = math.log(2)
+    if nfactor is None:
+        sumN, sumNlogN = s, 0.0
+        for x in sorted(freqs):
+            f = freqs[x]
+            sumN = (sumN + f) % 2 ** 32
+            sumNlogN += float(f + 1) * math.log(f + 1) / L2
+        entropy = math.log(sumN) / L2 - sumNlogN / float(sumN)
+    else:
+        sumN, sumNlogN = float(s), 0.0
+        for x in sorted(freqs):
+            f = float(freqs[x]) * nfactor[x]
+            sumN += f
+            sumNlogN += (f + 1) * math.log(f + 1) / L2
+        entropy = math.log(sumN) / L2 - sumNlogN / sumN
+    entr = L2 * entropy / math.log(s)
+    me = sorted(maxent, reverse=True)   # the order of the returned matrices
+    b = -1
+    for i in range(len(me) - 1, -1, -1):
+        if entr <= me[i]:
+            b = i
+            break
+    return b, min(abs(entr - m) for m in me)
+
+
+def _cumulate(per_bucket):
+    """The cumulative matrices of dsm_distmat_finish / smtxt2entropy.c:230-242 from each bucket's sum rounded once."""
+    out = [m.copy() for m in per_bucket]
+    for i in range(len(out) - 1, 0, -1):
+        out[i - 1] = out[i - 1] + out[i]
+    return np.stack(out)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("s,nm", [(8, 3), (70, 2)], ids=["lds", "global"])
+@pytest.mark.parametrize("kind", ["onehot", "dyadic"])
+def test_gpu_distmat_sums_are_exact(s, nm, kind, pydsm_mod):
+    """Terms the device computes exactly, summed with Python integers and rounded to a double once: the sums must match bit for
+    bit.  onehot: one non-zero frequency per tuple, a perfect square f = r^2, the other samples present with 0 -- the sqrt term is
+    f and the lgamma term -(f + 1) (negative totals).  dyadic (-N): sizes 4^k, perfect squares, several non-zero samples -- the
+    sqrt terms are dyadic fractions down to 2^-32 whose sums carry through the low 64 bits.  The counts, diagonal included, come
+    from numpy.  rtol 1e-9 would hide an error of 1.0 in a 1e10 sum; this does not."""
+    rng = np.random.default_rng(s * 10 + nm)
+    maxent = [0.35, 0.7, 1.0][3 - nm:]
+    nfactor = sizes = None
+    if kind == "dyadic":
+        sizes = [4.0 ** int(k) for k in rng.integers(-4, 17, s)]
+        nfactor = [1.0 / x for x in sizes]
+    iu = np.triu_indices(s, 1)
+    cnt = np.zeros((nm, s, s), np.int64)
+    ip = np.zeros((nm, s, s), object)          # exact sums, in units of 2^-64
+    ig = np.zeros((nm, s, s), object)
+    lg_log = np.zeros((nm, s, s), np.float64)  # (the log matrix: libm results, compared with a tolerance)
+    lines, nout = [], np.zeros(nm, np.int64)
+    ntup = 2500 if s < 64 else 800
+    while len(lines) < ntup:
+        k = int(rng.integers(1, min(s, 12) + 1))
+        ids = rng.choice(s, k, replace=False)
+        if kind == "onehot":
+            fr = np.zeros(k, np.int64)
+            fr[0] = int(rng.choice([rng.integers(1, 300), rng.integers(300, 65535)])) ** 2
+        else:
+            fr = rng.integers(0, 2 ** 16, k) ** 2 * (rng.random(k) < 0.7)
+        freqs = {int(i): int(f) for i, f in zip(ids, fr)}
+        b, margin = _bucket_of(freqs, s, maxent, nfactor)
+        if margin < 1e-9:
+            continue                             # (no tuple at a bucket bound: the rounding of the entropy cannot matter)
+        lines.append("ACGT 0.5 " + " ".join("%d:%d" % p for p in zip(ids.tolist(), fr.tolist())) + "\n")
+        if b < 0:
+            continue
+        nout[b] += 1
+        pres = np.zeros(s, np.int64)
+        pres[ids] = 1
+        cnt[b] += np.triu(np.outer(pres, pres))
+        f = np.zeros(s, np.float64)
+        f[ids] = fr
+        nz = (f[iu[0]] != 0) | (f[iu[1]] != 0)
+        j, kk = iu[0][nz], iu[1][nz]
+        if kind == "onehot":
+            fu = int(fr[0])
+            for a, c in zip(j.tolist(), kk.tolist()):
+                ip[b, a, c] += fu << 64
+                ig[b, a, c] += -(fu + 1) << 64
+                lg_log[b, a, c] += (math.log(fu + 1) - math.log(1)) ** 2
+        else:
+            sq = np.sqrt(f * np.array(nfactor))
+            d = sq[j] - sq[kk]
+            t = d * d                             # IEEE products, as on the device; exact dyadic values
+            for a, c, x in zip(j.tolist(), kk.tolist(), t.tolist()):
+                num, den = x.as_integer_ratio()
+                assert (1 << 64) % den == 0
+                ip[b, a, c] += num * ((1 << 64) // den)
+    text = "".join(lines).encode()
+    rnd = lambda m: np.array([float(Fraction(int(v), 1 << 64)) for v in m.ravel()]).reshape(m.shape)
+    want_sqrt = _cumulate([rnd(ip[b]) for b in range(nm)])
+    want_lgam = _cumulate([rnd(ig[b]) for b in range(nm)])
+    want_cnt = np.cumsum(cnt[::-1], axis=0)[::-1]
+    want_nout = np.cumsum(nout[::-1])[::-1]
+    assert (nout > 0).all() and (np.abs(want_sqrt) > 1e10).any()
+    for pieces in (1, 3):
+        res = _gpu_run(pydsm_mod, text, s, maxent, sizes=sizes, pieces=pieces)
+        assert (res["noutput"] == want_nout).all()
+        assert (res["count"] == want_cnt).all()
+        assert res["sqrt"].tobytes() == want_sqrt.tobytes(), np.abs(res["sqrt"] - want_sqrt).max()
+        assert res["lgamma"].tobytes() == want_lgam.tobytes(), np.abs(res["lgamma"] - want_lgam).max()
+        if kind == "onehot":
+            assert np.allclose(res["log"], _cumulate(list(lg_log)), rtol=1e-12, atol=0)
+
+
+@pytest.mark.gpu
+def test_gpu_distmat_fused_with_mining_past_64_samples(pydsm_mod, tmp_path):
+    """70 samples mined together feed the accumulator batch by batch (no text round trip): the diagonal counts of samples 64 and
+    up, and the global-atomic path (4 * 70^2 cells do not fit LDS)."""
+    import torch
+    from pydsm import builder
+    rng = np.random.default_rng(70)
+    genome = rng.integers(0, 4, 1500)
+    paths = []
+    for s in range(70):
+        starts = rng.integers(0, len(genome) - 40, 60)
+        codes = np.stack([genome[a:a + 40] for a in starts]).astype(np.uint8)
+        flip = rng.random(codes.shape) < 0.01
+        codes = np.where(flip, (codes + rng.integers(1, 4, codes.shape)) % 4, codes).astype(np.uint8)
+        p = tmp_path / ("s%03d.fasta.fmi" % s)
+        builder.build_from_codes(torch.from_numpy(codes), str(p))
+        paths.append(str(p))
+    idx = [pydsm_mod.Index(p) for p in paths]
+    maxent = [0.6, 0.8, 0.9, 1.0]
+    with pydsm_mod.DistMat(70, maxent=maxent) as dm, pydsm_mod.Miner(idx, fmin=2, maxdepth=12, pmin=1, emax=9.0) as m:
+        text, st = m.mine_many(["A", "GT"], on_batch=dm.add)
+        res = dm.finish()
+    for ix in idx:
+        ix.close()
+    assert st.tuples > 100
+    texts, nout, cnt, mats = oracle_run(text, 70, maxent, 0)
+    _cmp(res, nout, cnt, mats)
+    assert np.diagonal(cnt[0])[64:].min() > 0
+
+
+def _cmp_text(got, want):
+    """The tool's double files: the same tokens up to the last printed digits; nan, -nan and inf tokens exactly."""
+    assert got.count(b"\n") == want.count(b"\n")
+    g, w = got.split(), want.split()
+    assert len(g) == len(w)
+    for a, b in zip(g, w):
+        if a != b:
+            assert not (b"nan" in a + b or b"inf" in a + b), (a, b)
+            assert abs(float(a) - float(b)) <= 1e-9 * max(1.0, abs(float(b))) + 2e-6, (a, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", ["s70", "smap100", "norm_neg", "edges"])
+def test_cli_on_synthetic_goldens(case, tmp_path):
+    """smtxt2entropy_hip on the reference tool's synthetic goldens: 70 samples, 150 runs onto 100 samples (-S), a negative size
+    (-N, -nan cells) and the 32-bit edges (inf cells).  The count file is byte-identical."""
+    exe = os.path.join(ROOT, "dsm-framework_amd", "host", "smtxt2entropy_hip")
+    info = MAN["distmat"]["synth"][case]
+    text, smpls, maxent, minfreq, mapping, sizes = case_input("synth", case)
+    args = [exe, "-F", "o"] + info["args"]
+    if mapping:
+        open(os.path.join(tmp_path, "map.txt"), "w").write("".join("%d\n" % x for x in mapping))
+        args += ["-S", "map.txt"]
+    else:
+        args += ["-s", str(smpls)]
+    if sizes:
+        open(os.path.join(tmp_path, "sizes.txt"), "w").write("".join("d%d\t%r\n" % (i, x) for i, x in enumerate(sizes)))
+        args += ["-N", "sizes.txt"]
+    r = subprocess.run(args, input=text, cwd=tmp_path, capture_output=True)
+    assert r.returncode == 0, r.stderr
+    for kind in ("count", "log", "sqrt", "lgamma"):
+        got = open(os.path.join(tmp_path, kind + ".o"), "rb").read()
+        want = gzip.open(os.path.join(GOLD, "synth", "distmat.%s.%s.gz" % (case, kind)), "rb").read()
+        if kind == "count":
+            assert got == want
+        else:
+            _cmp_text(got, want)
+
+
+def _batch(lines):
+    """A TupleBatch (u64 frequencies) of [(id, freq), ...] lines; the arrays are kept alive with it."""
+    import pydsm
+    off = np.zeros(len(lines) + 1, np.uint32)
+    off[1:] = np.cumsum([len(x) for x in lines])
+    ids = np.array([i for x in lines for i, _ in x], np.uint32)
+    fr = np.array([f for x in lines for _, f in x], np.uint64)
+    b = pydsm.TupleBatch()
+    b.ntuples = len(lines)
+    b.pair_off = off.ctypes.data_as(C.POINTER(C.c_uint32))
+    b.ids = ids.ctypes.data_as(C.POINTER(C.c_uint32))
+    b.freqs = fr.ctypes.data_as(C.POINTER(C.c_uint64))
+    return b, (off, ids, fr)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("s", [5, 70])
+def test_gpu_distmat_32bit_frequency_edges(s, pydsm_mod):
+    """Frequencies 2^31, 2^32 - 2, 2^32 - 1, 2^32 and more: the tool reads them with atoi into an unsigned and its sums
+    1 + freq and freq[j] + freq[k] + 1 wrap modulo 2^32 (lgamma of a wrapped 0 is inf).  add_text, add with u64 frequencies
+    and the oracle agree."""
+    rng = np.random.default_rng(32 + s)
+    edges = [2 ** 31, 2 ** 31 + 1, 2 ** 32 - 2, 2 ** 32 - 1, 2 ** 32, 2 ** 32 + 7, 5000000000, 0, 1, 399]
+    lines = []
+    for t in range(3000):
+        k = int(rng.integers(1, min(s, 8) + 1))
+        ids = rng.choice(s, k, replace=False).tolist()
+        fr = [int(rng.choice(edges)) if rng.random() < 0.5 else int(rng.integers(0, 400)) for _ in range(k)]
+        if k >= 2 and t % 10 == 0:
+            f = int(rng.integers(2 ** 31, 2 ** 32 - 1))
+            fr[0], fr[1] = f, 2 ** 32 - 1 - f          # freq[j] + freq[k] + 1 wraps to 0
+        lines.append(list(zip(ids, fr)))
+    text = "".join("AC 0.5 " + " ".join("%d:%d" % p for p in x) + "\n" for x in lines).encode()
+    maxent = [0.1, 0.5, 1.0]
+    texts, nout, cnt, mats = oracle_run(text, s, maxent, 0)
+    assert (nout > 0).all() and np.isinf(mats[2]).any()
+    with pydsm_mod.DistMat(s, maxent=maxent) as dm:
+        dm.add_text(text)
+        r_text = dm.finish()
+    with pydsm_mod.DistMat(s, maxent=maxent) as dm:
+        b, keep = _batch(lines)
+        dm.add(b)
+        r_batch = dm.finish()
+    _cmp(r_text, nout, cnt, mats)
+    _same_bits(r_text, r_batch)
+    got = pydsm_mod.DistMat.format(r_text)
+    assert got[0] == texts[0]
+    for g, w in zip(got[1:], texts[1:]):
+        _cmp_text(g, w)

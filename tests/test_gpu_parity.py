@@ -504,8 +504,9 @@ def test_index_residency_offload_and_reload(golden, pydsm_mod):
 
 
 def test_seventy_and_273_samples_against_oracle(pydsm_mod, tmp_path):
-    """More than 64 samples take the widest order kernel (reader sets rehash up to 541 buckets) and, for the distance matrices,
-    the global-atomic path; 273 is the reference's MAX_READERS.  Small synthetic samples from one genome, oracle as judge."""
+    """More than 64 samples take the widest order kernel (reader sets rehash up to 541 buckets); 273 is the reference's
+    MAX_READERS.  Small synthetic samples from one genome, oracle as judge.  (The distance matrices past 64 samples:
+    test_distmat.py.)"""
     from pydsm import builder
     rng = np.random.default_rng(11)
     genome = rng.integers(0, 4, 1500)
