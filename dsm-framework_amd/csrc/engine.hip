@@ -2089,11 +2089,10 @@ class Engine {
     // one 16-byte load) -- up to eight samples: a sample's LF-step kernel then stores its words 2 * nlocal bytes apart, and with 64
     // samples that is one 128-byte line per 2-byte store (measured, 64 samples of 10^6 reads: 2171 ms per pass node-major, 1756 sample-major).
     bool node_major(bool w9) const { return w9 && nlocal > 1 && nlocal <= 8 && !trie_mode; }
-    bool dense_mode = true;     // DSM_DENSE=0: the sparse sweep on every level (A/B runs)
     u32 dense_min = 1u << 18;   // DSM_DENSE_MIN: narrowest level the dense sweep takes
-    bool pack_columns = true;   // levels whose frequencies are all below 512: one 16-bit column word per node (DSM_PACK=0 turns it off)
-    bool batch_mode = true;     // several samples: one launch per level for up to BATCH_MAX of this process's, handles derived in the kernel
-    bool self_mode = false;     // = several samples, index mode, batch_mode: no handle tables (see expand_tile, SELF)
+    // several samples, index mode: one launch per level for up to BATCH_MAX of this process's, handles derived in the kernel, no handle
+    // tables (see expand_tile, SELF)
+    bool self_mode = false;
     std::vector<u64*> splane2;  // self_mode: second plane buffer per sample (a level reads its parent level's planes while writing its own)
     u8* xsend = nullptr;
     u8* xrecv[2] = {nullptr, nullptr};
@@ -2116,7 +2115,6 @@ class Engine {
     size_t owned_bytes = 0;   // device bytes behind `owned` (page-rounded)
     Arena arena;
     Arena carena;          // one sample: the candidate records the advance sweep stores (a block that is cut to size after the level)
-    bool fold_cands = true;   // DSM_FOLD_CANDS=0: cand_store_kernel on every level (A/B runs)
     Arena earena;          // multi-rank: emission-side allocations
     Arena* ea = nullptr;   // &earena, or &arena in single-process runs
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -2203,15 +2201,11 @@ class Engine {
         DSM_HIP(hipSetDevice(device));
         size_t free_b = 0, total_b = 0;
         DSM_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (const char* e = getenv("DSM_BATCH")) batch_mode = atoi(e) != 0;
-        if (const char* e = getenv("DSM_PACK")) pack_columns = atoi(e) != 0;
-        if (const char* e = getenv("DSM_DENSE")) dense_mode = atoi(e) != 0;
         if (const char* e = getenv("DSM_DENSE_MIN")) dense_min = (u32)atol(e);
         spec_mode = d == 1 && !trie_mode && !multi;
-        if (const char* e = getenv("DSM_SPEC")) spec_mode = spec_mode && atoi(e) != 0;
         if (spec_mode) { if (int rc = dalloc(d_dyn, (size_t)4)) return rc; }
-        self_mode = d > 1 && !trie_mode && batch_mode;
-        if (owner_mode && !self_mode) return fail(DSM_E_INVAL, "owner_mode needs handles derived in the LF-step kernel (several samples, DSM_BATCH not 0)");
+        self_mode = d > 1 && !trie_mode;
+        if (owner_mode && !self_mode) return fail(DSM_E_INVAL, "owner_mode needs handles derived in the LF-step kernel (several samples)");
         // A frontier level holds disjoint suffix intervals, so it is never wider than the indexed text; the
         // union over d samples is bounded by the sum.  Size the default budget from that, not from the card.
         const u64 fbound = (world > 1 ? (u64)d * nmax : nsum) + 16;
@@ -2262,6 +2256,46 @@ class Engine {
             if (int rc = agree_min(mine, &agreed)) return rc;
             Fcap = (u32)agreed;
         }
+        if (int rc = alloc_levels(small_rec)) return rc;
+        // what this miner took so far (its own count: the card's free memory also moves with the other lanes and ranks of a card)
+        const size_t used = owned_bytes;
+        u64 arena_b = budget > used ? budget - used : 0;
+        const u64 floor_b = p.arena_bytes ? (1u << 20) : (64u << 20);  // an explicit budget is honoured down to 1 MiB
+        if (arena_b < floor_b) arena_b = floor_b;
+        if (multi) {
+            u64 agreed = 0;
+            if (int rc = agree_min(arena_b, &agreed)) return rc;
+            arena_b = agreed;
+        }
+        if (int rc = dalloc(arena.base, arena_b)) return rc;
+        arena.cap = arena_b;
+        ea = &arena;
+        if (multi && !stream_mode) {  // 60 % structure (identical on every rank), 40 % emission
+            arena.cap = (size_t)(arena_b * 0.6) & ~(size_t)255;
+            earena.base = arena.base + arena.cap;
+            earena.cap = arena_b - arena.cap;
+            ea = &earena;
+        }
+        if (d == 1 && !multi && !stream_mode && !trie_mode) {
+            // one sample mined: a sixteenth of the arena for the candidate records (16 B each; at the benchmark size one node in forty is a
+            // candidate and a level retains ≈12 B per node: the share is generous, and a level that does not fit is stored the old way)
+            carena.cap = (arena.cap / 16) & ~(size_t)255;
+            arena.cap -= carena.cap;
+            carena.base = arena.base + arena.cap;
+            if (const char* e = getenv("DSM_CAND_ARENA")) {   // test hook: a block so small that levels overflow it (they are stored the old way)
+                const size_t want = (size_t)atol(e) & ~(size_t)255;
+                if (want < carena.cap) carena.cap = want;
+            }
+        }
+        // (timing events without the system-scope fence a default event carries: the records bracket every LF-step launch, and a
+        // fence there would write the L2 back twice per level)
+        DSM_HIP(hipEventCreateWithFlags(&ev0, hipEventDisableSystemFence));
+        DSM_HIP(hipEventCreateWithFlags(&ev1, hipEventDisableSystemFence));
+        return 0;
+    }
+
+    // the buffers of the frontier levels, for Fcap nodes (small_rec: record buffers sized by the compact record, see FcapW)
+    int alloc_levels(bool small_rec) {
         // Record handles: four symbol segments of Seg handles, a tile of 256 parents owns 256 handles in each (see the record layout)
         Seg = (Fcap + TILE - 1) / TILE * TILE;
         Rcap = 4 * Seg;
@@ -2348,41 +2382,6 @@ class Engine {
         if (int rc = dalloc(d_pub_cmax, (size_t)(world > 0 ? world : 1))) return rc;
         DSM_HIP(hipHostMalloc((void**)&h_totals, 320 * sizeof(u32)));
         DSM_HIP(hipHostMalloc((void**)&h_childmax, (size_t)(world > 0 ? world : 1) * sizeof(u64)));
-        // what this miner took so far (its own count: the card's free memory also moves with the other lanes and ranks of a card)
-        const size_t used = owned_bytes;
-        u64 arena_b = budget > used ? budget - used : 0;
-        const u64 floor_b = p.arena_bytes ? (1u << 20) : (64u << 20);  // an explicit budget is honoured down to 1 MiB
-        if (arena_b < floor_b) arena_b = floor_b;
-        if (multi) {
-            u64 agreed = 0;
-            if (int rc = agree_min(arena_b, &agreed)) return rc;
-            arena_b = agreed;
-        }
-        if (int rc = dalloc(arena.base, arena_b)) return rc;
-        arena.cap = arena_b;
-        ea = &arena;
-        if (multi && !stream_mode) {  // 60 % structure (identical on every rank), 40 % emission
-            arena.cap = (size_t)(arena_b * 0.6) & ~(size_t)255;
-            earena.base = arena.base + arena.cap;
-            earena.cap = arena_b - arena.cap;
-            ea = &earena;
-        }
-        if (const char* e = getenv("DSM_FOLD_CANDS")) fold_cands = atoi(e) != 0;
-        if (d == 1 && !multi && !stream_mode && !trie_mode && fold_cands) {
-            // one sample mined: a sixteenth of the arena for the candidate records (16 B each; at the benchmark size one node in forty is a
-            // candidate and a level retains ≈12 B per node: the share is generous, and a level that does not fit is stored the old way)
-            carena.cap = (arena.cap / 16) & ~(size_t)255;
-            arena.cap -= carena.cap;
-            carena.base = arena.base + arena.cap;
-            if (const char* e = getenv("DSM_CAND_ARENA")) {   // test hook: a block so small that levels overflow it (they are stored the old way)
-                const size_t want = (size_t)atol(e) & ~(size_t)255;
-                if (want < carena.cap) carena.cap = want;
-            }
-        }
-        // (timing events without the system-scope fence a default event carries: the records bracket every LF-step launch, and a
-        // fence there would write the L2 back twice per level)
-        DSM_HIP(hipEventCreateWithFlags(&ev0, hipEventDisableSystemFence));
-        DSM_HIP(hipEventCreateWithFlags(&ev1, hipEventDisableSystemFence));
         return 0;
     }
 
@@ -2400,15 +2399,15 @@ class Engine {
         return 0;
     }
 
-    Xchg xview(int which, u64 F_, u64 bpr) const {
+    Xchg xview(int which, u32 F, bool w16, bool w9) const {  // the exchanged columns of a level of F nodes and class (w16, w9)
         Xchg x;
         x.base = xrecv[which];
-        x.bpr = bpr;
+        x.bpr = level_bytes(F, w16, w9);
         x.nlocal = (u32)nlocal;
         x.d = d;
-        x.F = F_;
-        x.fb = 0;
-        x.nm = 0;
+        x.F = F;
+        x.fb = col_bytes(w16, w9) - 1;
+        x.nm = node_major(w9) ? 1u : 0u;
         return x;
     }
 
@@ -2429,16 +2428,6 @@ class Engine {
         return evpool[k];
     }
 
-    // Runs one prefix.  mine: tuples to `tsink` (through the emitter thread); stream: wire bytes to `bsink`.
-    // emit_lo / emit_hi: only nodes with emit_lo <= depth <= emit_hi are filtered and emitted; expand_cap: nodes at that
-    // depth or deeper are not expanded.  Used when a prefix is split because a level did not fit (see MinerT::run_auto).
-    // seed / capture: reader-set iteration orders depend on the whole sibling structure above a node, so a sub-prefix
-    // run must start from the order its root had in the unsplit trie (captured by the shallow pass of the parent).
-    struct NodeOrder {
-        u32 depth = 0;
-        std::vector<u32> sym;               // capture: symbol of each node at `depth`
-        std::vector<std::vector<u16>> ord;  // capture: their orders; seed: ord[0]
-    };
     // Owner mode: between a level's gather and the broadcast that answers it the clients of the prefix wait for the owner.  Whatever
     // makes the owner leave in between (a failed call, a sink error, a limit) must still answer, or the clients would wait for ever:
     // the guard broadcasts BC_ABORT -- the same message size as the answer that was due -- when it goes out of scope armed.
@@ -2460,10 +2449,81 @@ class Engine {
             (void)e->prm.bcast(e->prm.owner_ctx, e->owner, e->bc_buf, bytes, (void*)e->st);
         }
     };
-    int run(const char* prefix_c, dsm_tuple_sink tsink, dsm_byte_sink bsink, void* ctx, bool emit = true, u32 emit_lo = 1,
-            u32 emit_hi = ~0u, u32 expand_cap = ~0u, const NodeOrder* seed = nullptr, NodeOrder* capture = nullptr, bool count = true) {
-        const std::string prefix = prefix_c ? prefix_c : "";
-        for (char ch : prefix)
+
+    // ---- the sizes of a level, by its class: w16 = every frequency fits 16 bits, w9 = ... and nine (one 16-bit word per node
+    // holds frequency and flags) -------------------------------------------------------------------------------------------------
+    // column bytes per node: the frequency, then the children nibble | left char << 4 (packed: the one word)
+    u32 col_bytes(bool w16, bool w9) const { return w9 ? 2u : (w16 ? 3u : (u32)sizeof(P) + 1); }
+    // one rank's exchange message: 16-byte header (largest child frequency of this level), [nlocal][F] frequencies, [nlocal][F] bytes,
+    // padding (packed levels: [nlocal][F] 16-bit words).  Owner mode: the owner gathers exactly what its clients send.
+    u64 level_bytes(u32 F, bool w16, bool w9) const { return (((u64)nlocal * F * col_bytes(w16, w9) + 15) & ~15ull) + 16; }
+    // owner mode: the answer to a level's gather, a 16-byte header and the union's child planes, 32 bytes per 64 parents
+    static size_t bcast_bytes(u32 F) { return 16 + (size_t)((F + 63) >> 6) * 32; }
+    // A level of wide records has the smaller capacity FcapW; every rank, and in owner mode every client, sees the same two numbers.
+    u32 level_cap(bool w16) const { return w16 ? Fcap : FcapW; }
+    int check_width(u32 Fn, bool w16) {
+        if (Fn > level_cap(w16)) return fail(DSM_E_CAPACITY, "frontier wider than the device buffers: use a longer prefix or a larger arena_bytes");
+        return 0;
+    }
+    // The word of a published packet (publish_kernel): width of the new level, its frequency class in bits 30-31
+    u32 decode_level(u32 word, bool* w16, bool* w9) const {
+        *w16 = !(word >> 31) && !trie_mode;    // the level's frequencies all fit 16 bits (parsed streams stay wide)
+        *w9 = *w16 && !((word >> 30) & 1u);   // ... and nine: frequency and flags share a 16-bit word
+        return word & 0x3FFFFFFFu;
+    }
+    // a reader-set order (its n readers in iteration order) for node 0 of order[k] (d <= 13: four bits per reader) / order16[k]
+    int upload_order(int k, const u16* ro, size_t n) {
+        if (d <= 13) {
+            u64 ord = 0;
+            for (size_t i = 0; i < n; ++i) ord |= (u64)ro[i] << (4 * i);
+            DSM_HIP(hipMemcpyAsync(order[k], &ord, sizeof(u64), hipMemcpyHostToDevice, st));
+        } else {
+            DSM_HIP(hipMemcpyAsync(order16[k], ro, n * sizeof(u16), hipMemcpyHostToDevice, st));
+        }
+        return 0;
+    }
+
+    // What one run keeps while it walks down the levels of its prefix; run() hands it to its phases.
+    struct Walk {
+        std::string prefix;
+        RunOpts o;
+        std::vector<LevelHost> L;  // the levels so far: L[l] holds the nodes of depth l
+        u32 order_mode = 0;        // reader-set orders kept: 0 none, 1 four bits per reader in one word (d <= 13), 2 one u16 per reader
+        bool emitting = false;     // cleared when this rank's emission side runs out of memory in a multi-rank run
+        bool emit_failed = false;
+        bool trace = false;        // DSM_TRACE_LEVELS: widths of the levels on stderr (debugging aid)
+        size_t nev = 0;            // timing events taken, two per LF-step launch
+        // The level being advanced.  depth & 1 is the ping-pong index of its buffers (rec, rp, nT, order) and of the exchange buffer
+        // that receives its columns.  Its class (w16, w9): every rank derives it from the same number, the largest frequency any sample
+        // has at that level, carried in the previous level's exchange (the root level is wide).
+        u32 F = 1, depth = 0;
+        bool w16 = false, w9 = false;
+        BcastGuard owed;           // (owner mode, on the owner: the answer to the level's gather, or the final verdict, is still due)
+        explicit Walk(Engine* e) : owed(e) {}
+        int cur() const { return (int)(depth & 1); }
+    };
+    // one level of the main path between its phases (advance, publish, commit)
+    struct Sweep {
+        Xchg x;                  // the level's exchanged columns
+        size_t mark = 0;         // arena offset of the provisional window for the children's arrays
+        u32* slot = nullptr;     // the window's links (self_mode)
+        bool filtered = false;   // the level's output predicates are evaluated; its candidates are stored after the wait
+        u32 crec_cap = 0;        // > 0: the sweep stores the level's candidates itself, up to that many records (see emit_store)
+        u32 Fn = 0;              // the children's level: width and class, from the published packet
+        bool w16 = false, w9 = false;
+        bool spec_hit = false;   // the LF-step launch queued ahead of the wait took the children's level
+    };
+
+    // Runs one prefix.  mine: tuples to `tsink` (through the emitter thread); stream: wire bytes to `bsink`.  `o` cuts the run (RunOpts).
+    // One level after the other: the exchange of its columns, the advance sweep to its children, the publish kernel whose packet the host
+    // waits for, and the children's LF-step launch.  The LF-step launch of a level is queued as early as possible: for level L+1 right after
+    // the synchronisation of level L, ahead of that level's remaining small launches (order, candidate store), so the GPU does not wait for
+    // the host to get through them; with one sample it is even queued before the wait (spec_mode).
+    int run(const char* prefix_c, dsm_tuple_sink tsink, dsm_byte_sink bsink, void* ctx, const RunOpts& o = RunOpts()) {
+        Walk w(this);
+        w.prefix = prefix_c ? prefix_c : "";
+        w.o = o;
+        for (char ch : w.prefix)
             if (ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T')
                 return fail(DSM_E_INVAL, "prefix must be over A,C,G,T");  // anything else has an empty LF interval: nothing to send
         DSM_HIP(hipSetDevice(device));
@@ -2472,16 +2532,55 @@ class Engine {
         arena.off = 0;
         earena.off = 0;
         carena.off = 0;
-        bool emitting = emit;       // cleared when this rank's emission side runs out of memory in a multi-rank run
-        bool emit_failed = false;
-        std::vector<LevelHost> L;
-        L.reserve(512);
+        w.emitting = o.emit;
+        w.L.reserve(512);
         DSM_HIP(hipMemsetAsync(d_counters, 0, (size_t)COUNTER_SHARDS * 8 * sizeof(u64), st));
         if (cntraw) DSM_HIP(hipMemsetAsync(cntraw, 0, (4 * (size_t)(Seg / TILE) + 8) * sizeof(u32), st));  // a run that failed mid-level may have left counts
         DSM_HIP(hipEventRecord(ev0, st));
-        size_t nev = 0;
+        if (int rc = root_level(w)) return rc;
+        // pmax == 1 (sample-specific substrings, BASELINE configs[4]): every printed node has one reader, its single pair needs no
+        // order, and nothing else depends on the reader sets' iteration orders -- the order kernels are skipped altogether
+        w.order_mode = (d < 2 || prm.pmax == 1) ? 0u : (d <= 13 ? 1u : 2u);
+        stats.pair_order_exact = 1;
+        w.trace = getenv("DSM_TRACE_LEVELS") != nullptr;
+        DSM_HIP(hipMemsetAsync(multi ? xsend : xrecv[0], 0, XHDR, st));  // later levels: cleared by publish_kernel
+        if (int rc = launch_lf(w, 0, 1, w.w16, w.w9, w.L[0].slot)) return rc;
+        while (true) {
+            if (int rc = exchange(w)) return rc;
+            if (owner_mode && !is_owner) {
+                bool more = false;
+                if (int rc = client_level(w, &more)) return rc;
+                if (!more) break;
+                continue;
+            }
+            if (owner_mode) { if (int rc = owner_precheck(w)) return rc; }
+            Sweep s;
+            LevelHost child;
+            if (int rc = advance(w, s)) return rc;
+            if (int rc = publish(w, s)) return rc;
+            if (int rc = commit(w, s, child)) return rc;
+            if (int rc = capture_level(w, s.Fn, child.slot, child.pw)) return rc;
+            if (s.filtered) {  // the candidates of this level: totals arrived with the synchronisation above
+                int erc = emit_store(w.L[w.depth], w.F, w.depth, s.x, w.cur(), w.order_mode, s.crec_cap);
+                if (erc == DSM_E_CAPACITY && multi) { w.emit_failed = true; w.emitting = false; }
+                else if (erc) return erc;
+            }
+            DSM_HIP(hipGetLastError());
+            if (pend.submit && (w.F >= 200000u || w.depth >= 24)) { if (int rc = flush_pending()) return rc; }  // the previous prefix's tuples may leave now
+            count_level(w);
+            if (!s.Fn) break;
+            w.L.push_back(child);
+            step(w, s.Fn, s.w16, s.w9);
+            if (w.L.size() > 60000) return fail(DSM_E_CAPACITY, "trie deeper than 60000 levels");
+        }
+        timeline("levels done", w.prefix.c_str());
+        if (int rc = flush_pending()) return rc;  // (a prefix that never got wide or deep)
+        if (int rc = finish_prefix(w, tsink, bsink, ctx)) return rc;
+        return read_back(w);
+    }
 
-        // ---- level 0: the root (EnumerateQuery::enumerate, EnumerateQuery.cpp:9-37) --------------
+    // ---- level 0: the root (EnumerateQuery::enumerate, EnumerateQuery.cpp:9-37) --------------
+    int root_level(Walk& w) {
         const char* bases = "ACGT";
         for (int s = 0; s < nlocal && trie_mode; ++s) {  // the root of a parsed stream is its node 0
             const u32 zero = 0;
@@ -2512,542 +2611,513 @@ class Engine {
             stats.lf_steps += 8;
             for (int a = 0; a < 4; ++a) stats.rank_ops += 2 * m.lfcost[a];
         }
-        {
-            LevelHost root;
-            root.n = 1;
-            ARENA_GET(root.slot, u32, 1);
-            ARENA_GET(root.pw, uint2, 1);
-            if (int rc = alloc_kids(root)) return rc;
-            if (self_mode) DSM_HIP(hipMemsetAsync(root.slot, 0, sizeof(u32), st));
-            DSM_HIP(hipMemsetAsync(root.pw, 0, sizeof(uint2), st));
-            L.push_back(root);
-            u16 rootT = (u16)d;
-            DSM_HIP(hipMemcpyAsync(nT[0], &rootT, sizeof(u16), hipMemcpyHostToDevice, st));
-            // root reader set: ids inserted 0..d-1 (metaserver.cpp:736-739)
-            std::vector<u16> seq(d), ro(d + 1), tmp(so_work_size(d, d));
-            for (u32 k = 0; k < d; ++k) seq[k] = (u16)k;
-            set_iteration_order<u16>(seq.data(), d, ro.data(), tmp.data(), d);
-            if (d <= 13) {
-                u64 ord = 0;
-                for (u32 k = 0; k < d; ++k) ord |= (u64)ro[k] << (4 * k);
-                DSM_HIP(hipMemcpyAsync(order[0], &ord, sizeof(u64), hipMemcpyHostToDevice, st));
-            } else {
-                DSM_HIP(hipMemcpyAsync(order16[0], ro.data(), (size_t)d * sizeof(u16), hipMemcpyHostToDevice, st));
-            }
-        }
-        // pmax == 1 (sample-specific substrings, BASELINE configs[4]): every printed node has one reader, its single pair needs no
-        // order, and nothing else depends on the reader sets' iteration orders -- the order kernels are skipped altogether
-        const u32 order_mode = (d < 2 || prm.pmax == 1) ? 0u : (d <= 13 ? 1u : 2u);  // (declared before the level loop: used by seed/capture)
-        stats.pair_order_exact = 1;
+        LevelHost root;
+        root.n = 1;
+        ARENA_GET(root.slot, u32, 1);
+        ARENA_GET(root.pw, uint2, 1);
+        if (int rc = alloc_kids(root)) return rc;
+        if (self_mode) DSM_HIP(hipMemsetAsync(root.slot, 0, sizeof(u32), st));
+        DSM_HIP(hipMemsetAsync(root.pw, 0, sizeof(uint2), st));
+        w.L.push_back(root);
+        u16 rootT = (u16)d;
+        DSM_HIP(hipMemcpyAsync(nT[0], &rootT, sizeof(u16), hipMemcpyHostToDevice, st));
+        // root reader set: ids inserted 0..d-1 (metaserver.cpp:736-739)
+        std::vector<u16> seq(d), ro(d + 1), tmp(so_work_size(d, d));
+        for (u32 k = 0; k < d; ++k) seq[k] = (u16)k;
+        set_iteration_order<u16>(seq.data(), d, ro.data(), tmp.data(), d);
+        return upload_order(0, ro.data(), d);
+    }
 
-        // Width of the frequency column of the level about to be exchanged.  Every rank derives it from the same number: the
-        // largest frequency any sample has at that level, carried in the previous level's exchange (the root level is wide).
-        bool w16 = false;
-        bool w9 = false;   // ... and below 512: one 16-bit word per node holds frequency and flags
-        int cur = 0;      // ping-pong index of the current level (rec, rp, nT, order)
-        int xcur = 0;     // exchange buffer that will receive the current level's children
-        u32 F = 1;
-        u32 depth = 0;
-        // The expand launch of a level is queued as early as possible: for level L+1 right after the synchronisation of
-        // level L, ahead of that level's remaining small launches (order, candidate store), so the GPU does not wait for
-        // the host to get through them.
-        const bool trace_levels = getenv("DSM_TRACE_LEVELS") != nullptr;  // debugging aid: widths of the levels on stderr
-        bool fmt_in = false;  // format of the records of the level about to be expanded (the root's record is wide)
-        // dynamic: F is not known yet (0 is passed): the kernel takes the width from d_dyn and runs only if the level's class is (w16, w9)
-        // (dynamic launches: Fmax bounds the level -- four children per node of the level before it -- so a small level is not
-        // swept by the whole resident grid)
-        auto launch_expand = [&](u32 F, u32 depth, int cur, int xcur, bool w16, bool w9, const u32* lslot, bool fmt_in, bool dynamic, u64 Fmax = ~0ull) -> int {
-            // ---- expand ---------------------------------------------------------------------------
-            const u64 slots = (u64)F * 4;
-            const u32 fb = w9 ? 1u : (w16 ? 2u : (u32)sizeof(P));
-            const u32 colb = w9 ? 2u : fb + 1;  // column bytes per node
-            // per rank: 16-byte header (largest child frequency of this level), [nlocal][F] frequencies, [nlocal][F] bytes, padding
-            // (packed levels: [nlocal][F] 16-bit words)
-            const u64 bpr = (((u64)nlocal * F * colb + 15) & ~15ull) + 16;
-            const int nxt = cur ^ 1;
-            u8* send = multi ? xsend : xrecv[xcur];
-            ExpandArgs ea;
-            memset(&ea, 0, sizeof ea);
-            ea.F = F; ea.nbp = (F + TILE - 1) / TILE; ea.fmin = prm.fmin; ea.w16 = w9 ? 2u : (w16 ? 1u : 0u);
-            // handle spaces: the children's records are compact iff this level is narrow (w16), this level's iff its parent level was (fmt_in)
-            ea.seg = seg_of(w16 && !trie_mode); ea.cap = 4 * ea.seg;
-            ea.seg_in = seg_of(fmt_in); ea.cap_in = 4 * ea.seg_in;
-            const bool nm = node_major(w9);  // node-major packed columns (Xchg::nm)
-            ea.cstride = nm ? (u32)nlocal : 1u;
-            if (dynamic) {
-                ea.dyn = d_dyn;
-                ea.dyn_mask = pack_columns ? 3u : 1u;
-                ea.dyn_expect = ((w16 ? 0u : 1u) | (w9 ? 0u : 2u)) & ea.dyn_mask;
-                ea.fcap = w16 ? Fcap : FcapW;
-            }
-            unsigned long long* d_childmax = reinterpret_cast<unsigned long long*>(send);  // header, cleared by the previous level's publish kernel
-            if (depth < prefix.size()) {
-                const char* q = strchr(bases, prefix[depth]);
-                ea.allowed = 1u << (q - bases);
-                ea.symbol_phase = 0;
-            } else {
-                ea.allowed = (depth >= prm.maxdepth || depth >= expand_cap) ? 0u : 15u;  // EnumerateQuery.cpp:153
-                ea.symbol_phase = 1;
-            }
-            // `reported` counts a node once however a prefix was split: a run counts the depths it is responsible for
-            if (count && depth + 1 >= emit_lo && depth + 1 <= emit_hi) ea.symbol_phase |= 2u;
-            if (d == 1 && !trie_mode) {  // one sample: the output predicates of this level's nodes are evaluated by its LF-step kernel
-                ea.symbol_phase |= 8u;
-                const bool emit_level = !stream_mode && emit && depth >= 1 && depth >= emit_lo && depth <= emit_hi;
-                const bool ent_ok = !(prm.emax > 0 && (0.0 < prm.emin - ENT_MARGIN || 0.0 > prm.emax + ENT_MARGIN));
-                if (emit_level && depth >= prm.mindepth && prm.pmin <= 1 && ent_ok) ea.symbol_phase |= 4u;
-            }
-            ea.probe_slot = 1u + 3u * ((u32)(nev / 2) % (u32)((COUNTER_SHARDS - 4) / 3));  // (read by DSM_CLOCK_PROBE builds of expand.hip only)
-            hipEvent_t ea0 = pool_event(nev++), ea1 = pool_event(nev++);
-            if (!ea0 || !ea1) return fail(DSM_E_HIP, "hipEventCreate failed");
-            std::unique_lock<std::mutex> chain_lock(g_expand_chain.mu);
-            ExpandChain::Link& link = g_expand_chain.dev[device];
-            if (link.last && link.owner != this) DSM_HIP(hipStreamWaitEvent(st, link.last, 0));
-            DSM_HIP(hipEventRecord(ea0, st));
-            for (int s = 0; s < nlocal && trie_mode; ++s) {  // children, frequency and left char come from the parsed stream
-                const dsm_trie* t = tries[s];
-                P* cf = reinterpret_cast<P*>(send + XHDR + (size_t)s * F * fb);
-                u8* cl = send + XHDR + (size_t)nlocal * F * fb + (size_t)s * F;
-                if (depth + 1 < t->level_off.size()) {
-                    const u64 o = t->level_off[depth];
-                    hipLaunchKernelGGL((trie_expand_kernel<P>), grid_for(F), dim3(256), 0, st, F, rp[cur][s], t->d_freq + o, t->d_pl + o, t->d_fc + o, cf, cl, tpos[s], ea.allowed);
-                } else {  // deeper than this sample's trie: it holds none of these nodes
-                    DSM_HIP(hipMemsetAsync(cf, 0, (size_t)F * fb, st));
-                    DSM_HIP(hipMemsetAsync(cl, 0, (size_t)F, st));
-                }
-            }
-            ExpandBatch eb;
-            int nb = 0;
-            bool all_one_sb = true;
-            for (int s = 0; s < nlocal && !trie_mode; ++s) all_one_sb = all_one_sb && (idx[s]->meta.n >> SB_SHIFT) == 0;
-            for (int s = 0; s < nlocal && !trie_mode; ++s) {
-                const IndexMeta& m = idx[s]->meta;
-                ExpandSample& es = eb.s[nb];
-                es.ix = idx[s]->dev;
-                es.rp = rp[cur][s]; es.rec = rec[cur][s]; es.out = rec[nxt][s]; es.splane = splane[s];
-                es.pplane = nullptr;
-                if (self_mode) {  // handles from the level's slots and the planes of the parent level (the two plane buffers alternate)
-                    es.rp = lslot;
-                    es.splane = (depth & 1) ? splane2[s] : splane[s];
-                    es.pplane = (depth & 1) ? splane[s] : splane2[s];
-                }
-                es.valf = send + XHDR + (nm ? (size_t)s * 2 : (size_t)s * F * (w9 ? 2u : fb));  // this sample's frequency column (packed: its words)
-                es.pl = send + XHDR + (size_t)nlocal * F * fb + (size_t)s * F;   // children nibble | left char << 4 (not used when packed)
-                for (int c = 0; c < 4; ++c) es.cost[c] = m.lfcost[c];
-                for (int c = 0; c < 4; ++c) es.sb.sb0[c] = m.C[(int)(unsigned char)bases[c]];  // superblock 0: nothing before it
-                es.costsum_lo = es.costsum_hi = 0;
-                for (u32 set = 0; set < 16; ++set) {
-                    u64 sum = 0;
-                    for (int c = 0; c < 4; ++c) sum += ((set >> c) & 1u) ? m.lfcost[c] : 0u;
-                    if (sum > 63) return fail(DSM_E_UNSUPPORTED, "Huffman codes too long for the cost table");
-                    if (set < 10) es.costsum_lo |= sum << (6 * set); else es.costsum_hi |= sum << (6 * (set - 10));
-                }
-                es.access_pack = 0; es.pad = 0;
-                for (int c = 0; c < 8; ++c) {
-                    const u32 bits = c < m.ncodes ? m.codes[m.code2byte[c]].bits : 0;
-                    if (bits > 15) return fail(DSM_E_UNSUPPORTED, "Huffman code longer than 15 bits");
-                    es.access_pack |= bits << (4 * c);
-                }
-                ++nb;
-                stats.expand_slots += F;
-                stats.expand_column_bytes += (u64)F * colb;
-                LfConfig lc;
-                lc.wide_pos = sizeof(P) == 8; lc.fmt_in = fmt_in; lc.fmt_out = w16;
-                // several samples: a sample holds a fraction of the union level (half with eight 1-Gbase samples, a fifth with 64): on the
-                // levels wide enough to keep every wave busy with items, each sample's own nodes are packed into full tiles (expand.hip)
-                lc.dense = dense_mode && self_mode && fmt_in && F >= dense_min;
-                // record formats: this level's records are compact iff its parent level was narrow (fmt_in), the children's iff this one is
-                if (self_mode) {  // several samples: one launch for up to BATCH_MAX of this process's
-                    if (nb < BATCH_MAX && s + 1 < nlocal) continue;
-                    static const u32 grid_factor = getenv("DSM_BATCH_GRID_FACTOR") ? (u32)atoi(getenv("DSM_BATCH_GRID_FACTOR")) : 1u;
-                    lc.one_sb = all_one_sb;
-                    lf_step_launch_batch(lc, lfgeo, grid_factor ? grid_factor : 1u, nb, st, eb, ea, d_counters, d_childmax);
-                    nb = 0;
-                    ++stats.expand_launches;
-                    continue;
-                }
-                nb = 0;
-                ea.sb = es.sb;
-                for (int c = 0; c < 4; ++c) ea.cost[c] = es.cost[c];
-                ea.access_pack = es.access_pack; ea.costsum_lo = es.costsum_lo; ea.costsum_hi = es.costsum_hi;
-                lc.one_sb = (m.n >> SB_SHIFT) == 0;
-                u32* ecnt = nullptr;  // (round 4: the tile counts of a single sample are counted from its planes by lite_count_kernel, not by atomics here)
-                // (a launch queued ahead: Fmax bounds the level -- four children per node of the level before it)
-                const u64 tiles_bound = dynamic ? (Fmax == ~0ull ? ~0ull >> 8 : (Fmax + 63) / 64) : ((u64)F + 63) / 64;
-                lf_step_launch(lc, lfgeo, tiles_bound, st, idx[s]->dev, rp[cur][s], rec[cur][s], rec[nxt][s], splane[s], ecnt, es.valf, es.pl, ea, d_counters,
-                               d_childmax);
-                ++stats.expand_launches;
-            }
-            DSM_HIP(hipEventRecord(ea1, st));
-            link.last = ea1; link.owner = this;
-            chain_lock.unlock();
-            DSM_HIP(hipGetLastError());
-            return 0;
-        };
-        DSM_HIP(hipMemsetAsync(multi ? xsend : xrecv[xcur], 0, XHDR, st));  // later levels: cleared by publish_kernel
-        if (int rc = launch_expand(F, depth, cur, xcur, w16, w9, L[0].slot, fmt_in, false)) return rc;
-        fmt_in = w16 && !trie_mode;  // the next level's records are compact iff this level is narrow
-        BcastGuard owed(this);  // (owner mode, on the owner: the answer to the level's gather, or the final verdict, is still due)
-        static const int test_owner_fail = getenv("DSM_TEST_OWNER_FAIL") ? atoi(getenv("DSM_TEST_OWNER_FAIL")) : -1;  // test hook: the owner fails at this depth
-        while (true) {
-            const u64 slots = (u64)F * 4;
-            const u32 fb = w9 ? 1u : (w16 ? 2u : (u32)sizeof(P));
-            const u64 bpr = (((u64)nlocal * F * (w9 ? 2u : fb + 1) + 15) & ~15ull) + 16;
-            const int nxt = cur ^ 1;
-            // ---- exchange: one all-gather per level, or (owner mode) columns to the owner and the union's child planes back -------
-            if (multi && !owner_mode) {
-                int rc = prm.allgather(prm.allgather_ctx, xsend, xrecv[xcur], (size_t)bpr, (void*)st);
-                if (rc) return fail(DSM_E_SINK, "allgather callback failed");
-                stats.exchange_bytes_sent += bpr;
-                stats.exchange_bytes_received += bpr * (u64)(world - 1);
-            }
-            const u32 nwv = (F + 63) >> 6;
-            const size_t bc_bytes = 16 + (size_t)nwv * 32;
-            if (owner_mode) {
-                owed.disarm();  // (the gather that was owed is this one; if it fails the communicator is gone and nobody can be told)
-                if (prm.gather(prm.owner_ctx, owner, xsend, xrecv[xcur], (size_t)bpr, (void*)st)) return fail(DSM_E_SINK, "gather callback failed");
-                if (!is_owner) {
-                    // ---- a client of this prefix: wait for the owner's verdict on the level, then only the links of the next one ----
-                    stats.exchange_bytes_sent += bpr;
-                    if (prm.bcast(prm.owner_ctx, owner, bc_buf, bc_bytes, (void*)st)) return fail(DSM_E_SINK, "bcast callback failed");
-                    stats.exchange_bytes_received += bc_bytes;
-                    u32 hdr[4] = {0, 0, 0, 0};
-                    DSM_HIP(hipMemcpyAsync(hdr, bc_buf, 16, hipMemcpyDeviceToHost, st));
-                    DSM_HIP(hipStreamSynchronize(st));
-                    if (hdr[0] == BC_CAPACITY) return fail(DSM_E_CAPACITY, "the prefix does not fit the owner's device arena: use a longer prefix or a larger arena_bytes");
-                    if (hdr[0] == BC_ABORT) return fail(DSM_E_SINK, "the prefix's owner failed and aborted the prefix (its own error says why)");
-                    if (hdr[0] != BC_OK) return fail(DSM_E_HIP, "malformed broadcast from the prefix's owner");
-                    const u32 Fn = hdr[1] & 0x3FFFFFFFu;
-                    w16 = !(hdr[1] >> 31);
-                    w9 = w16 && !((hdr[1] >> 30) & 1u) && pack_columns;
-                    stats.union_nodes += depth >= 1 ? F : 0;
-                    if (F > stats.max_frontier) stats.max_frontier = F;
-                    ++stats.levels;
-                    if (trace_levels) fprintf(stderr, "dsm level prefix=%s depth=%u F=%u (client of rank %d)\n", prefix.c_str(), depth, F, owner);
-                    if (Fn > (w16 ? Fcap : FcapW)) return fail(DSM_E_CAPACITY, "frontier wider than the device buffers: use a longer prefix or a larger arena_bytes");
-                    if (!Fn) break;
-                    const u64* planes = reinterpret_cast<const u64*>(bc_buf + 16);
-                    const u32 nbp = (F + TILE - 1) / TILE;
-                    if (nbp > 1) {
-                        hipLaunchKernelGGL(lite_count_kernel, dim3((nbp + 63) / 64), dim3(256), 0, st, planes, nwv, cnt4, nbp, 2u);
-                        exclusive_scan<u32, u32>(cnt4, cnt4, (size_t)4 * nbp, scan_tmp, d_totals, st);
-                    }
-                    hipLaunchKernelGGL(lite_slot_kernel, dim3(nbp), dim3(256), 0, st, planes, F, cnt4, nbp, nbp == 1 ? 1u : 0u, lite_slot[nxt], Fcap);
-                    DSM_HIP(hipGetLastError());
-                    if (capture && depth + 1 == capture->depth) {  // (which bases continue the prefix: every rank enumerates the same sub-prefixes)
-                        std::vector<u32> hs(Fn);
-                        DSM_HIP(hipMemcpyAsync(hs.data(), lite_slot[nxt], (size_t)Fn * sizeof(u32), hipMemcpyDeviceToHost, st));
-                        DSM_HIP(hipStreamSynchronize(st));
-                        capture->sym.clear();
-                        capture->ord.clear();
-                        for (u32 v = 0; v < Fn; ++v) { capture->sym.push_back(hs[v] & 3u); capture->ord.push_back(std::vector<u16>(1, 0)); }
-                    }
-                    if (int rc = launch_expand(Fn, depth + 1, nxt, xcur ^ 1, w16, w9, lite_slot[nxt], fmt_in, false)) return rc;
-                    fmt_in = w16 && !trie_mode;
-                    cur = nxt;
-                    xcur ^= 1;
-                    F = Fn;
-                    ++depth;
-                    continue;
-                }
-                stats.exchange_bytes_received += bpr * (u64)(world - 1);
-                owed.arm(bc_bytes);  // from here to the broadcast below every way out answers the clients (BC_ABORT)
-                if (test_owner_fail >= 0 && (int)depth == test_owner_fail) return fail(DSM_E_SINK, "injected owner failure (DSM_TEST_OWNER_FAIL)");
-                // the owner: whatever this level may allocate must fit before anything is sent back -- a failure later would leave the
-                // clients waiting.  (Emission-side allocations only flag a failure, see emit_failed.)
-                const size_t wc = (size_t)F * 4 < Fcap ? (size_t)F * 4 : Fcap;
-                const size_t need = wc * 12 + 512 + ((wc + TILE - 1) / TILE * 4) * 48 + 4096;
-                if (arena.off + need > arena.cap) {
-                    const u32 hdr[4] = {BC_CAPACITY, 0, 0, 0};
-                    DSM_HIP(hipMemcpyAsync(bc_buf, hdr, 16, hipMemcpyHostToDevice, st));
-                    DSM_HIP(hipStreamSynchronize(st));
-                    owed.disarm();
-                    if (prm.bcast(prm.owner_ctx, owner, bc_buf, bc_bytes, (void*)st)) return fail(DSM_E_SINK, "bcast callback failed");
-                    return fail(DSM_E_CAPACITY, "device arena exhausted: use a longer prefix or a larger arena_bytes");
-                }
-            }
-            Xchg x = xview(xcur, F, bpr);
-            x.fb = fb;
-            x.nm = node_major(w9) ? 1u : 0u;
-            // ---- union frontier of the next level -------------------------------------------------
-            LevelHost& me = L[depth];
-            LevelHost child;
-            // the arena hands out memory past `off`; the new level's arrays are claimed after Fn is known, so
-            // the down-sweep writes into a provisional window that is then committed
-            if (stream_mode && depth >= 1) {  // this level's own frequencies / left chars complete its records for the wire stream
-                ARENA_GET(me.srec, uint4, F);
-                ARENA_GET(me.clen, u8, F);
-                hipLaunchKernelGGL((keep_kernel<P>), grid_for(F), dim3(256), 0, st, F, x, sa[cur], me.srec, me.clen);
-            }
-            const bool emit_here = !stream_mode && emitting && depth >= 1 && depth >= emit_lo && depth <= emit_hi;
-            bool filtered = false;
-            if (emit_here) {
-                int erc = emit_alloc(me, F);
-                if (erc == DSM_E_CAPACITY && multi) { emit_failed = true; emitting = false; }  // agreed on at the end of the prefix
-                else if (erc) return erc;
-                else filtered = true;
-            }
-            const size_t mark2 = arena.off;
-            // What a level retains per node: the links (4 * parent + symbol) where something reads them -- the wire stream, handles
-            // derived inside the LF-step kernel -- and the path words when tuples are mined.  With both, the words follow the links,
-            // whose length only the device knows when the sweep runs: the window is sized for the widest level possible here.
-            const bool keep_slot = self_mode, keep_pw = !stream_mode;  // (stream mode: records, completed at the node's own level)
-            const size_t wcap = (size_t)F * 4 < Fcap ? (size_t)F * 4 : Fcap;
-            u8* window = arena.get<u8>(wcap * ((keep_slot ? 4 : 0) + (keep_pw ? 8 : 0)) + 512);
-            if (!window) return fail(DSM_E_CAPACITY, "device arena exhausted: use a longer prefix or a larger arena_bytes");
-            u32* new_slot2 = keep_slot ? reinterpret_cast<u32*>(window) : nullptr;
-            const u32 nbp = (F + TILE - 1) / TILE;  // tiles of this level
-            AdvanceOut ao;
-            memset(&ao, 0, sizeof ao);
-            ao.slot = new_slot2; ao.nT = nT[nxt]; ao.samechild = samechild;
-            if (stream_mode) ao.sa = sa[nxt];
-            if (keep_pw) {
-                ao.pw = reinterpret_cast<uint2*>(window);  // (behind the links: the kernels place it, see pw_after_slot)
-                ao.pw_after_slot = keep_slot ? 1u : 0u;
-                ao.parent_pw = me.pw;
-                ao.plevel = depth;
-            }
-            ao.parent_nT = nT[cur]; ao.nlocal = (u32)nlocal; ao.rank = (u32)rank;
-            ao.cap = (u32)((size_t)F * 4 < Fcap ? (size_t)F * 4 : Fcap);
-            ao.seg = seg_of(w16 && !trie_mode);  // (of the records this level's LF-step launch wrote: the children's)
-            ao.h_totals = d_pub_tot;
-            ao.rp = d_rp_tab[nxt];
-            ao.rp0 = rp[nxt][0];
-            ao.tpos = trie_mode ? d_tpos_tab : nullptr;
-            ao.splane = d_splane_tab;
-            ao.rp_index = self_mode ? 0u : 1u;
-            ao.kcum = me.kcum; ao.cnt4 = cnt4; ao.nbp = nbp; ao.kshift = 2;
-            ao.width = d_totals;  // (levels of several tiles: the scan's grand total)
-            const bool merged = d > 1 || trie_mode;  // the union of several columns (a parsed stream is treated alike)
-            if (merged && nbp == 1) {  // a single tile evaluates the columns itself
-                ao.eval = 1; ao.kplane_w = me.kplane;
-            } else if (merged) {
-                hipLaunchKernelGGL((advance_reduce_kernel<P>), dim3(nbp), dim3(256), 0, st, x, sinfo, me.kplane, cnt4, nbp);
-                ao.kplane = me.kplane; ao.sinfo = sinfo;
-            } else {                   // one sample: the union trie is its trie, the expand kernel wrote planes and tile counts
-                ao.kplane = splane[0]; ao.kplane_w = me.kplane; ao.single = 1;
-                ao.kshift = 3;
-            }
-            static const bool lean_sweep = !(getenv("DSM_LEAN_ADVANCE") && atoi(getenv("DSM_LEAN_ADVANCE")) == 0);
-            const bool lean = lean_sweep && !merged && nbp > 1 && keep_pw && !keep_slot && !stream_mode;   // advance_single_kernel takes the level
-            // One sample: the level's candidates are stored by the sweep itself.  Their number is known only after it: the records go
-            // to a block of their own arena, taken as large as the level could need and cut to size after the synchronisation.
-            bool fold = false;
-            u32 crec_cap = 0;
-            if (lean && filtered && carena.cap) {
-                const size_t room = (carena.cap - carena.off) / sizeof(uint4);
-                crec_cap = (u32)(room < (size_t)F ? room : (size_t)F);
-                fold = crec_cap > 0;
-            }
-            if (nbp > 1) {
-                // one sample: the tile counts from the planes its LF-step kernel wrote (that kernel added them up with four atomics per
-                // tile of 64 nodes before: 470 K memory-side atomics per launch of the wide levels); with them the candidates per tile
-                if (!merged) hipLaunchKernelGGL(lite_count_kernel, dim3((nbp + 63) / 64), dim3(256), 0, st, splane[0], (F + 63) >> 6, cntraw, nbp, 3u, fold ? 1u : 0u);
-                exclusive_scan<u32, u32>(merged ? cnt4 : cntraw, cnt4, (size_t)(fold ? 5 : 4) * nbp, scan_tmp, d_totals, st);
-            }
-            // ---- the output predicates for the nodes of THIS level (their children are known now) ride in the wave sweep; the scan of
-            // the candidate counts is queued ahead of the wait ----
-            const bool fused_filter = filtered && nbp > 1;
-            if (fused_filter) {
-                ao.fa = filter_args(F, depth, order_mode); ao.candbits = me.cand_bits; ao.wsum = cand_wsum;
-                if (ao.single) ao.cand_copy = 1;  // (the level's LF-step kernel decided: the sweep only moves the words into place)
-                else ao.filter_on = 1;
-            }
-            if (fold) { ao.crec = reinterpret_cast<uint4*>(carena.base + carena.off); ao.crec_cap = crec_cap; }
-            if (nbp == 1) hipLaunchKernelGGL((advance_down_kernel<P>), dim3(1), dim3(256), 0, st, x, ao);
-            else if (lean) hipLaunchKernelGGL((advance_single_kernel<P>), dim3((nbp + 3) / 4), dim3(256), 0, st, x, ao);
-            else hipLaunchKernelGGL((advance_wave_kernel<P>), dim3(nbp), dim3(256), 0, st, x, ao);
-            if (filtered) {
-                if (int erc = emit_filter(me, F, depth, x, cur, order_mode, !fused_filter, fold)) return erc;
-            }
-            {
-                PublishArgs pa;
-                memset(&pa, 0, sizeof pa);
-                pa.total = nbp == 1 ? d_pub_tot : d_totals;  // new level's width: from the single tile, or the scan's total
-                pa.cmax_base = x.base; pa.cmax_bpr = x.bpr; pa.cmax_world = (u32)world;
-                if (filtered) pa.cand = d_totals64;
-                if (fold) {  // the scan ran over the child counts and, behind them, the candidate counts: the width is what it had reached there
-                    pa.total = cnt4 + (size_t)4 * nbp;
-                    pa.grand = d_totals;
-                    pa.cand = nullptr;
-                }
-                pa.clear = reinterpret_cast<u32*>(multi ? xsend : xrecv[xcur ^ 1]);  // where the next level's expand reports its child maximum
-                pa.packet = reinterpret_cast<uint4*>(h_totals + 304); pa.seq = ++pub_seq;
-                pa.next = spec_mode ? d_dyn : nullptr;
-                pa.bc_header = owner_mode ? reinterpret_cast<uint4*>(bc_buf) : nullptr;
-                hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(64), 0, st, pa);
-            }
-            if (owner_mode) {  // the union's child planes of this level follow the header: what a client needs to go on
-                DSM_HIP(hipMemcpyAsync(bc_buf + 16, me.kplane, (size_t)nwv * 32, hipMemcpyDeviceToDevice, st));
-                owed.disarm();
-                if (prm.bcast(prm.owner_ctx, owner, bc_buf, bc_bytes, (void*)st)) return fail(DSM_E_SINK, "bcast callback failed");
-                stats.exchange_bytes_sent += bc_bytes * (u64)(world - 1);
-            }
-            // ---- the next level's LF-step launch goes out now, sized on the device, assuming the level is of this level's frequency
-            // class (the largest frequency only falls with depth: a prefix changes class twice); the host catches up below ----
-            const bool spec = spec_mode;
-            const bool spec_w16 = w16, spec_w9 = w9;
-            if (spec) { if (int rc = launch_expand(0, depth + 1, nxt, xcur ^ 1, spec_w16, spec_w9, new_slot2, fmt_in, true, (u64)F * 4)) return rc; }
-            u32 pk[4];
-            {   // the publish kernel is the last work queued: its packet in pinned memory is this level's completion.  Spinning on
-                // it returns a few microseconds after the store; a stream synchronisation wakes the thread later.
-                volatile u32* fl = h_totals + 304;
-                u32 spins = 0;
-                while (*fl != pub_seq) {
-                    if ((++spins & 0xFFFFu) == 0 && hipStreamQuery(st) != hipErrorNotReady) {  // finished (or failed) without the packet?
-                        DSM_HIP(hipStreamSynchronize(st));
-                        if (*fl != pub_seq) return fail(DSM_E_HIP, "publish kernel did not report");
-                        break;
-                    }
-                    __builtin_ia32_pause();
-                }
-                std::atomic_thread_fence(std::memory_order_acquire);
-                for (int q = 0; q < 4; ++q) pk[q] = fl[q];
-            }
-            const u32 Fn = pk[1] & 0x3FFFFFFFu;
-            w16 = !(pk[1] >> 31) && !trie_mode;  // the next level's frequencies all fit 16 bits (parsed streams stay wide)
-            w9 = w16 && !((pk[1] >> 30) & 1u) && pack_columns;  // ... and nine: frequency and flags share a 16-bit word
-            // did the launch queued ahead run?  (the kernel tested the same two words the packet carries)
-            const bool spec_hit = spec && Fn > 0 && Fn <= (w16 ? Fcap : FcapW) && w16 == spec_w16 && (!pack_columns || ((pk[1] >> 30) & 1u) == (spec_w9 ? 0u : 1u));
-            if (spec && !spec_hit) --stats.expand_launches;  // (the launch queued ahead found no level, or another class, and did nothing)
-            h_totals[300] = pk[2]; h_totals[301] = pk[3];  // candidate totals of this level (read by emit_store)
-            // (a level of wide records has the smaller capacity FcapW; every rank, and in owner mode every client, sees the same two numbers)
-            if (Fn > (w16 ? Fcap : FcapW)) return fail(DSM_E_CAPACITY, "frontier wider than the device buffers: use a longer prefix or a larger arena_bytes");
-            if (owner_mode) {  // what the clients do next: send the next level's columns and wait for its answer, or wait for the final verdict
-                if (!Fn) owed.arm(16);
-                else owed.arm_next((size_t)((((u64)nlocal * Fn * (w9 ? 2u : (w16 ? 3u : (u32)sizeof(P) + 1)) + 15) & ~15ull) + 16), xrecv[xcur ^ 1], 16 + (size_t)((Fn + 63) >> 6) * 32);
-            }
-            // commit the provisional window at its real size
-            arena.off = mark2;
-            child.n = Fn;
-            if (Fn) {
-                if (keep_slot) child.slot = arena.get<u32>(Fn);   // same address as new_slot2
-                if (keep_pw) child.pw = arena.get<uint2>(Fn);     // the window's start, or right behind the links (256-byte granules, as the kernels assume)
-                if (int rc = alloc_kids(child)) return rc;
-                if (spec_hit) {
-                    stats.expand_slots += Fn;
-                    stats.expand_column_bytes += (u64)Fn * (w9 ? 2u : (w16 ? 3u : (u32)sizeof(P) + 1));
-                } else {
-                    if (int rc = launch_expand(Fn, depth + 1, nxt, xcur ^ 1, w16, w9, child.slot, fmt_in, false)) return rc;  // w16, w9 already describe the next level
-                }
-                fmt_in = w16 && !trie_mode;
-                // orders are only needed by a rank that emits this prefix (and by the shallow pass that captures them)
-                if (!(emit || capture)) {}
-                else if (order_mode == 1)
-                    hipLaunchKernelGGL((order_kernel<P>), grid_for(F), dim3(256), 0, st, F, x, nT[cur], order[cur], me.kids(), order[nxt]);
-                else if (order_mode == 2 && d <= 64)
-                    hipLaunchKernelGGL((order_big_kernel<P, 64>), grid_for(F, 64), dim3(64), 0, st, F, x, nT[cur], order16[cur], me.kids(), order16[nxt]);
-                else if (order_mode == 2)
-                    hipLaunchKernelGGL((order_big_kernel<P, 273>), grid_for(F, 64), dim3(64), 0, st, F, x, nT[cur], order16[cur], me.kids(), order16[nxt]);
-            }
-            if (Fn && order_mode && seed && depth + 1 == seed->depth) {  // the sub-prefix root keeps its order from the unsplit trie
-                const std::vector<u16>& so = seed->ord[0];
-                if (order_mode == 1) {
-                    u64 ord = 0;
-                    for (size_t k = 0; k < so.size(); ++k) ord |= (u64)so[k] << (4 * k);
-                    DSM_HIP(hipMemcpyAsync(order[nxt], &ord, sizeof(u64), hipMemcpyHostToDevice, st));
-                } else {
-                    DSM_HIP(hipMemcpyAsync(order16[nxt], so.data(), so.size() * sizeof(u16), hipMemcpyHostToDevice, st));
-                }
-            }
-            if (Fn && capture && depth + 1 == capture->depth) {
-                std::vector<u32> hs(Fn);
-                std::vector<u16> hn(Fn);
-                if (child.slot) DSM_HIP(hipMemcpyAsync(hs.data(), child.slot, (size_t)Fn * sizeof(u32), hipMemcpyDeviceToHost, st));
-                else if (stream_mode) {  // the symbol sits in the second word of the sweep's (parent, flags) pair
-                    std::vector<uint2> hr(Fn);
-                    DSM_HIP(hipMemcpyAsync(hr.data(), sa[nxt], (size_t)Fn * sizeof(uint2), hipMemcpyDeviceToHost, st));
-                    DSM_HIP(hipStreamSynchronize(st));
-                    for (u32 v = 0; v < Fn; ++v) hs[v] = hr[v].y & 3u;
-                } else {  // the last symbol of the node's path word
-                    std::vector<uint2> hp(Fn);
-                    DSM_HIP(hipMemcpyAsync(hp.data(), child.pw, (size_t)Fn * sizeof(uint2), hipMemcpyDeviceToHost, st));
-                    DSM_HIP(hipStreamSynchronize(st));
-                    for (u32 v = 0; v < Fn; ++v) hs[v] = (hp[v].y >> (2 * (depth % PW_CHUNK))) & 3u;
-                }
-                DSM_HIP(hipMemcpyAsync(hn.data(), nT[nxt], (size_t)Fn * sizeof(u16), hipMemcpyDeviceToHost, st));
-                DSM_HIP(hipStreamSynchronize(st));
-                capture->sym.clear();
-                capture->ord.clear();
-                for (u32 v = 0; v < Fn; ++v) {
-                    capture->sym.push_back(hs[v] & 3);
-                    std::vector<u16> o(d == 1 ? 1 : hn[v]);  // (a single sample keeps no reader counts)
-                    if (order_mode == 1) {
-                        u64 ord = 0;
-                        DSM_HIP(hipMemcpy(&ord, order[nxt] + v, sizeof(u64), hipMemcpyDeviceToHost));
-                        for (u32 k = 0; k < hn[v]; ++k) o[k] = (u16)((ord >> (4 * k)) & 15);
-                    } else if (order_mode == 2) {
-                        DSM_HIP(hipMemcpy(o.data(), order16[nxt] + (size_t)v * d, (size_t)hn[v] * sizeof(u16), hipMemcpyDeviceToHost));
-                    }
-                    capture->ord.push_back(o);
-                }
-            }
-            if (filtered) {  // the candidates of this level: totals arrived with the synchronisation above
-                int erc = emit_store(me, F, depth, x, cur, order_mode, fold ? crec_cap : 0u);
-                if (erc == DSM_E_CAPACITY && multi) { emit_failed = true; emitting = false; }
-                else if (erc) return erc;
-            }
-            DSM_HIP(hipGetLastError());
-            if (trace_levels) fprintf(stderr, "dsm level prefix=%s depth=%u F=%u\n", prefix.c_str(), depth, F);
-            if (pend.submit && (F >= 200000u || depth >= 24)) { if (int rc = flush_pending()) return rc; }  // the previous prefix's tuples may leave now
-            stats.union_nodes += depth >= 1 ? F : 0;
-            if (F > stats.max_frontier) stats.max_frontier = F;
-            ++stats.levels;
-            if (!Fn) break;
-            L.push_back(child);
-            cur = nxt;
-            xcur ^= 1;
-            F = Fn;
-            ++depth;
-            if (L.size() > 60000) return fail(DSM_E_CAPACITY, "trie deeper than 60000 levels");
+    // ---- the LF-step launch of the level at `depth` (F nodes of class w16, w9; lslot: its links): the children's columns go to the
+    // exchange buffer.  Fmax > 0: the launch is queued before the host has seen the level -- F is not known yet (0 is passed), the
+    // kernel takes the width from d_dyn and runs only if the level is of the class (w16, w9); Fmax, four children per node of the
+    // level before, bounds it, so that a small level is not swept by the whole resident grid.
+    int launch_lf(Walk& w, u32 depth, u32 F, bool w16, bool w9, const u32* lslot, u64 Fmax = 0) {
+        const char* bases = "ACGT";
+        const bool dynamic = Fmax != 0;
+        // handle spaces: the children's records are compact iff this level is narrow (w16), this level's iff its parent level -- the one
+        // being advanced -- is (the root's record is wide)
+        const bool fmt_in = depth > 0 && w.w16 && !trie_mode;
+        const int cur = (int)(depth & 1), nxt = cur ^ 1;
+        const u32 colb = col_bytes(w16, w9), fb = colb - 1;  // (fb: bytes of a frequency)
+        u8* send = multi ? xsend : xrecv[cur];
+        ExpandArgs ea;
+        memset(&ea, 0, sizeof ea);
+        ea.F = F; ea.nbp = (F + TILE - 1) / TILE; ea.fmin = prm.fmin; ea.w16 = w9 ? 2u : (w16 ? 1u : 0u);
+        ea.seg = seg_of(w16 && !trie_mode); ea.cap = 4 * ea.seg;
+        ea.seg_in = seg_of(fmt_in); ea.cap_in = 4 * ea.seg_in;
+        const bool nm = node_major(w9);  // node-major packed columns (Xchg::nm)
+        ea.cstride = nm ? (u32)nlocal : 1u;
+        if (dynamic) {
+            ea.dyn = d_dyn;
+            ea.dyn_mask = 3u;
+            ea.dyn_expect = (w16 ? 0u : 1u) | (w9 ? 0u : 2u);
+            ea.fcap = level_cap(w16);
         }
-        const u32 nlev = (u32)L.size();  // levels 0..nlev-1, level l holds the nodes of depth l
-        timeline("levels done", prefix.c_str());
-        if (int rc = flush_pending()) return rc;  // (a prefix that never got wide or deep)
-
-        bool ready = false;
-        if (stream_mode) {
-            if (emit) { if (int rc = finish_stream(L, nlev, bsink, ctx)) return rc; }
+        unsigned long long* d_childmax = reinterpret_cast<unsigned long long*>(send);  // header, cleared by the previous level's publish kernel
+        if (depth < w.prefix.size()) {
+            const char* q = strchr(bases, w.prefix[depth]);
+            ea.allowed = 1u << (q - bases);
+            ea.symbol_phase = 0;
         } else {
-            if (emitting) {
-                int rc = finish_mine(L, nlev, tsink, ctx, &ready);
-                if (rc == DSM_E_CAPACITY && multi) { emit_failed = true; ready = false; }
-                else if (rc) return rc;
-            }
-            if (owner_mode) {  // only the owner emits: its word on the emission side reaches the clients with one last broadcast
-                u32 hdr[4] = {emit_failed ? BC_CAPACITY : BC_OK, 0, 0, 0};
-                if (is_owner) {
-                    DSM_HIP(hipMemcpyAsync(bc_buf, hdr, 16, hipMemcpyHostToDevice, st));
-                    DSM_HIP(hipStreamSynchronize(st));
-                }
-                owed.disarm();
-                if (prm.bcast(prm.owner_ctx, owner, bc_buf, 16, (void*)st)) return fail(DSM_E_SINK, "bcast callback failed");
-                if (!is_owner) {
-                    DSM_HIP(hipMemcpyAsync(hdr, bc_buf, 16, hipMemcpyDeviceToHost, st));
-                    DSM_HIP(hipStreamSynchronize(st));
-                }
-                if (hdr[0] == BC_ABORT) return fail(DSM_E_SINK, "the prefix's owner failed and aborted the prefix (its own error says why)");
-                if (hdr[0] != BC_OK) return fail(DSM_E_CAPACITY, "device arena exhausted on the prefix's owner: use a longer prefix or a larger arena_bytes");
-            } else if (multi) {  // every rank learns whether some rank's emission side overflowed: split together or not at all
-                u64 ok = emit_failed ? 0 : 1, all_ok = 0;
-                if (int rc = agree_min(ok, &all_ok)) return rc;
-                if (!all_ok) return fail(DSM_E_CAPACITY, "device arena exhausted on a rank: use a longer prefix or a larger arena_bytes");
-            }
-            if (ready) pend.submit = true;   // (the set is prepared; flush_pending hands it over once the next prefix is under way)
-            else pend.E = nullptr;
-            static const bool defer = !(getenv("DSM_DEFER_EMIT") && atoi(getenv("DSM_DEFER_EMIT")) == 0);  // (0: at once, for A/B runs)
-            if (!defer) { if (int rc = flush_pending()) return rc; }
+            ea.allowed = (depth >= prm.maxdepth || depth >= w.o.expand_cap) ? 0u : 15u;  // EnumerateQuery.cpp:153
+            ea.symbol_phase = 1;
         }
+        // `reported` counts a node once however a prefix was split: a run counts the depths it is responsible for
+        if (w.o.count && depth + 1 >= w.o.emit_lo && depth + 1 <= w.o.emit_hi) ea.symbol_phase |= 2u;
+        if (d == 1 && !trie_mode) {  // one sample: the output predicates of this level's nodes are evaluated by its LF-step kernel
+            ea.symbol_phase |= 8u;
+            const bool emit_level = !stream_mode && w.o.emit && depth >= 1 && depth >= w.o.emit_lo && depth <= w.o.emit_hi;
+            const bool ent_ok = !(prm.emax > 0 && (0.0 < prm.emin - ENT_MARGIN || 0.0 > prm.emax + ENT_MARGIN));
+            if (emit_level && depth >= prm.mindepth && prm.pmin <= 1 && ent_ok) ea.symbol_phase |= 4u;
+        }
+        ea.probe_slot = 1u + 3u * ((u32)(w.nev / 2) % (u32)((COUNTER_SHARDS - 4) / 3));  // (read by DSM_CLOCK_PROBE builds of expand.hip only)
+        hipEvent_t ea0 = pool_event(w.nev++), ea1 = pool_event(w.nev++);
+        if (!ea0 || !ea1) return fail(DSM_E_HIP, "hipEventCreate failed");
+        std::unique_lock<std::mutex> chain_lock(g_expand_chain.mu);
+        ExpandChain::Link& link = g_expand_chain.dev[device];
+        if (link.last && link.owner != this) DSM_HIP(hipStreamWaitEvent(st, link.last, 0));
+        DSM_HIP(hipEventRecord(ea0, st));
+        for (int s = 0; s < nlocal && trie_mode; ++s) {  // children, frequency and left char come from the parsed stream
+            const dsm_trie* t = tries[s];
+            P* cf = reinterpret_cast<P*>(send + XHDR + (size_t)s * F * fb);
+            u8* cl = send + XHDR + (size_t)nlocal * F * fb + (size_t)s * F;
+            if (depth + 1 < t->level_off.size()) {
+                const u64 o = t->level_off[depth];
+                hipLaunchKernelGGL((trie_expand_kernel<P>), grid_for(F), dim3(256), 0, st, F, rp[cur][s], t->d_freq + o, t->d_pl + o, t->d_fc + o, cf, cl, tpos[s], ea.allowed);
+            } else {  // deeper than this sample's trie: it holds none of these nodes
+                DSM_HIP(hipMemsetAsync(cf, 0, (size_t)F * fb, st));
+                DSM_HIP(hipMemsetAsync(cl, 0, (size_t)F, st));
+            }
+        }
+        ExpandBatch eb;
+        int nb = 0;
+        bool all_one_sb = true;
+        for (int s = 0; s < nlocal && !trie_mode; ++s) all_one_sb = all_one_sb && (idx[s]->meta.n >> SB_SHIFT) == 0;
+        for (int s = 0; s < nlocal && !trie_mode; ++s) {
+            const IndexMeta& m = idx[s]->meta;
+            ExpandSample& es = eb.s[nb];
+            es.ix = idx[s]->dev;
+            es.rp = rp[cur][s]; es.rec = rec[cur][s]; es.out = rec[nxt][s]; es.splane = splane[s];
+            es.pplane = nullptr;
+            if (self_mode) {  // handles from the level's slots and the planes of the parent level (the two plane buffers alternate)
+                es.rp = lslot;
+                es.splane = (depth & 1) ? splane2[s] : splane[s];
+                es.pplane = (depth & 1) ? splane[s] : splane2[s];
+            }
+            es.valf = send + XHDR + (nm ? (size_t)s * 2 : (size_t)s * F * (w9 ? 2u : fb));  // this sample's frequency column (packed: its words)
+            es.pl = send + XHDR + (size_t)nlocal * F * fb + (size_t)s * F;   // children nibble | left char << 4 (not used when packed)
+            for (int c = 0; c < 4; ++c) es.cost[c] = m.lfcost[c];
+            for (int c = 0; c < 4; ++c) es.sb.sb0[c] = m.C[(int)(unsigned char)bases[c]];  // superblock 0: nothing before it
+            es.costsum_lo = es.costsum_hi = 0;
+            for (u32 set = 0; set < 16; ++set) {
+                u64 sum = 0;
+                for (int c = 0; c < 4; ++c) sum += ((set >> c) & 1u) ? m.lfcost[c] : 0u;
+                if (sum > 63) return fail(DSM_E_UNSUPPORTED, "Huffman codes too long for the cost table");
+                if (set < 10) es.costsum_lo |= sum << (6 * set); else es.costsum_hi |= sum << (6 * (set - 10));
+            }
+            es.access_pack = 0; es.pad = 0;
+            for (int c = 0; c < 8; ++c) {
+                const u32 bits = c < m.ncodes ? m.codes[m.code2byte[c]].bits : 0;
+                if (bits > 15) return fail(DSM_E_UNSUPPORTED, "Huffman code longer than 15 bits");
+                es.access_pack |= bits << (4 * c);
+            }
+            ++nb;
+            stats.expand_slots += F;
+            stats.expand_column_bytes += (u64)F * colb;
+            LfConfig lc;
+            lc.wide_pos = sizeof(P) == 8; lc.fmt_in = fmt_in; lc.fmt_out = w16;
+            // several samples: a sample holds a fraction of the union level (half with eight 1-Gbase samples, a fifth with 64): on the
+            // levels wide enough to keep every wave busy with items, each sample's own nodes are packed into full tiles (expand.hip)
+            lc.dense = self_mode && fmt_in && F >= dense_min;
+            if (self_mode) {  // several samples: one launch for up to BATCH_MAX of this process's
+                if (nb < BATCH_MAX && s + 1 < nlocal) continue;
+                lc.one_sb = all_one_sb;
+                lf_step_launch_batch(lc, lfgeo, 1u, nb, st, eb, ea, d_counters, d_childmax);  // (one workgroup share per sample)
+                nb = 0;
+                ++stats.expand_launches;
+                continue;
+            }
+            nb = 0;
+            ea.sb = es.sb;
+            for (int c = 0; c < 4; ++c) ea.cost[c] = es.cost[c];
+            ea.access_pack = es.access_pack; ea.costsum_lo = es.costsum_lo; ea.costsum_hi = es.costsum_hi;
+            lc.one_sb = (m.n >> SB_SHIFT) == 0;
+            u32* ecnt = nullptr;  // (round 4: the tile counts of a single sample are counted from its planes by lite_count_kernel, not by atomics here)
+            const u64 tiles_bound = ((dynamic ? Fmax : (u64)F) + 63) / 64;
+            lf_step_launch(lc, lfgeo, tiles_bound, st, idx[s]->dev, rp[cur][s], rec[cur][s], rec[nxt][s], splane[s], ecnt, es.valf, es.pl, ea, d_counters,
+                           d_childmax);
+            ++stats.expand_launches;
+        }
+        DSM_HIP(hipEventRecord(ea1, st));
+        link.last = ea1; link.owner = this;
+        chain_lock.unlock();
+        DSM_HIP(hipGetLastError());
+        return 0;
+    }
 
-        DSM_HIP(hipEventRecord(ev1, st));
-        timeline("finish queued", prefix.c_str());
+    // ---- exchange: one all-gather per level, or (owner mode) columns to the owner and the union's child planes back ----
+    int exchange(Walk& w) {
+        if (!multi) return 0;
+        const u64 bpr = level_bytes(w.F, w.w16, w.w9);
+        if (!owner_mode) {
+            if (prm.allgather(prm.allgather_ctx, xsend, xrecv[w.cur()], (size_t)bpr, (void*)st)) return fail(DSM_E_SINK, "allgather callback failed");
+            stats.exchange_bytes_sent += bpr;
+            stats.exchange_bytes_received += bpr * (u64)(world - 1);
+            return 0;
+        }
+        w.owed.disarm();  // (the gather that was owed is this one; if it fails the communicator is gone and nobody can be told)
+        if (prm.gather(prm.owner_ctx, owner, xsend, xrecv[w.cur()], (size_t)bpr, (void*)st)) return fail(DSM_E_SINK, "gather callback failed");
+        if (is_owner) stats.exchange_bytes_received += bpr * (u64)(world - 1);
+        else stats.exchange_bytes_sent += bpr;
+        return 0;
+    }
+
+    // ---- a client of this prefix (owner mode): wait for the owner's verdict on the level, then only the links of the next one ----
+    int client_level(Walk& w, bool* more) {
+        const u32 F = w.F;
+        const int nxt = w.cur() ^ 1;
+        const size_t bc_bytes = bcast_bytes(F);
+        if (prm.bcast(prm.owner_ctx, owner, bc_buf, bc_bytes, (void*)st)) return fail(DSM_E_SINK, "bcast callback failed");
+        stats.exchange_bytes_received += bc_bytes;
+        u32 hdr[4] = {0, 0, 0, 0};
+        DSM_HIP(hipMemcpyAsync(hdr, bc_buf, 16, hipMemcpyDeviceToHost, st));
         DSM_HIP(hipStreamSynchronize(st));
-        timeline("device done", prefix.c_str());
+        if (hdr[0] == BC_CAPACITY) return fail(DSM_E_CAPACITY, "the prefix does not fit the owner's device arena: use a longer prefix or a larger arena_bytes");
+        if (hdr[0] == BC_ABORT) return fail(DSM_E_SINK, "the prefix's owner failed and aborted the prefix (its own error says why)");
+        if (hdr[0] != BC_OK) return fail(DSM_E_HIP, "malformed broadcast from the prefix's owner");
+        bool w16 = false, w9 = false;
+        const u32 Fn = decode_level(hdr[1], &w16, &w9);
+        count_level(w);
+        if (int rc = check_width(Fn, w16)) return rc;
+        *more = Fn > 0;
+        if (!Fn) return 0;
+        const u64* planes = reinterpret_cast<const u64*>(bc_buf + 16);
+        const u32 nwv = (F + 63) >> 6;
+        const u32 nbp = (F + TILE - 1) / TILE;
+        if (nbp > 1) {
+            hipLaunchKernelGGL(lite_count_kernel, dim3((nbp + 63) / 64), dim3(256), 0, st, planes, nwv, cnt4, nbp, 2u);
+            exclusive_scan<u32, u32>(cnt4, cnt4, (size_t)4 * nbp, scan_tmp, d_totals, st);
+        }
+        hipLaunchKernelGGL(lite_slot_kernel, dim3(nbp), dim3(256), 0, st, planes, F, cnt4, nbp, nbp == 1 ? 1u : 0u, lite_slot[nxt], Fcap);
+        DSM_HIP(hipGetLastError());
+        if (int rc = capture_level(w, Fn, lite_slot[nxt], nullptr)) return rc;  // (which bases continue the prefix: every rank enumerates the same sub-prefixes)
+        if (int rc = launch_lf(w, w.depth + 1, Fn, w16, w9, lite_slot[nxt])) return rc;
+        step(w, Fn, w16, w9);
+        return 0;
+    }
+
+    // ---- the owner (owner mode): whatever this level may allocate must fit before anything is sent back -- a failure later would
+    // leave the clients waiting.  (Emission-side allocations only flag a failure, see emit_failed.) ----
+    int owner_precheck(Walk& w) {
+        static const int test_owner_fail = getenv("DSM_TEST_OWNER_FAIL") ? atoi(getenv("DSM_TEST_OWNER_FAIL")) : -1;  // test hook: the owner fails at this depth
+        const size_t bc_bytes = bcast_bytes(w.F);
+        w.owed.arm(bc_bytes);  // from here to the level's broadcast every way out answers the clients (BC_ABORT)
+        if (test_owner_fail >= 0 && (int)w.depth == test_owner_fail) return fail(DSM_E_SINK, "injected owner failure (DSM_TEST_OWNER_FAIL)");
+        const size_t wc = (size_t)w.F * 4 < Fcap ? (size_t)w.F * 4 : Fcap;
+        const size_t need = wc * 12 + 512 + ((wc + TILE - 1) / TILE * 4) * 48 + 4096;
+        if (arena.off + need <= arena.cap) return 0;
+        const u32 hdr[4] = {BC_CAPACITY, 0, 0, 0};
+        DSM_HIP(hipMemcpyAsync(bc_buf, hdr, 16, hipMemcpyHostToDevice, st));
+        DSM_HIP(hipStreamSynchronize(st));
+        w.owed.disarm();
+        if (prm.bcast(prm.owner_ctx, owner, bc_buf, bc_bytes, (void*)st)) return fail(DSM_E_SINK, "bcast callback failed");
+        return fail(DSM_E_CAPACITY, "device arena exhausted: use a longer prefix or a larger arena_bytes");
+    }
+
+    // ---- the advance sweep of a level: the union frontier of its children, and the output predicates of its own nodes (their
+    // children are known now) riding in the wave sweep; the scan of the candidate counts is queued ahead of the wait ----
+    int advance(Walk& w, Sweep& s) {
+        const u32 F = w.F, depth = w.depth;
+        const int cur = w.cur(), nxt = cur ^ 1;
+        s.x = xview(cur, F, w.w16, w.w9);
+        const Xchg& x = s.x;
+        LevelHost& me = w.L[depth];
+        // the arena hands out memory past `off`; the new level's arrays are claimed after Fn is known, so
+        // the down-sweep writes into a provisional window that is then committed
+        if (stream_mode && depth >= 1) {  // this level's own frequencies / left chars complete its records for the wire stream
+            ARENA_GET(me.srec, uint4, F);
+            ARENA_GET(me.clen, u8, F);
+            hipLaunchKernelGGL((keep_kernel<P>), grid_for(F), dim3(256), 0, st, F, x, sa[cur], me.srec, me.clen);
+        }
+        if (!stream_mode && w.emitting && depth >= 1 && depth >= w.o.emit_lo && depth <= w.o.emit_hi) {
+            int erc = emit_alloc(me, F);
+            if (erc == DSM_E_CAPACITY && multi) { w.emit_failed = true; w.emitting = false; }  // agreed on at the end of the prefix
+            else if (erc) return erc;
+            else s.filtered = true;
+        }
+        s.mark = arena.off;
+        // What a level retains per node: the links (4 * parent + symbol) where something reads them -- the wire stream, handles
+        // derived inside the LF-step kernel -- and the path words when tuples are mined.  With both, the words follow the links,
+        // whose length only the device knows when the sweep runs: the window is sized for the widest level possible here.
+        const bool keep_slot = self_mode, keep_pw = !stream_mode;  // (stream mode: records, completed at the node's own level)
+        const size_t wcap = (size_t)F * 4 < Fcap ? (size_t)F * 4 : Fcap;
+        u8* window = arena.get<u8>(wcap * ((keep_slot ? 4 : 0) + (keep_pw ? 8 : 0)) + 512);
+        if (!window) return fail(DSM_E_CAPACITY, "device arena exhausted: use a longer prefix or a larger arena_bytes");
+        s.slot = keep_slot ? reinterpret_cast<u32*>(window) : nullptr;
+        const u32 nbp = (F + TILE - 1) / TILE;  // tiles of this level
+        AdvanceOut ao;
+        memset(&ao, 0, sizeof ao);
+        ao.slot = s.slot; ao.nT = nT[nxt]; ao.samechild = samechild;
+        if (stream_mode) ao.sa = sa[nxt];
+        if (keep_pw) {
+            ao.pw = reinterpret_cast<uint2*>(window);  // (behind the links: the kernels place it, see pw_after_slot)
+            ao.pw_after_slot = keep_slot ? 1u : 0u;
+            ao.parent_pw = me.pw;
+            ao.plevel = depth;
+        }
+        ao.parent_nT = nT[cur]; ao.nlocal = (u32)nlocal; ao.rank = (u32)rank;
+        ao.cap = (u32)wcap;
+        ao.seg = seg_of(w.w16 && !trie_mode);  // (of the records this level's LF-step launch wrote: the children's)
+        ao.h_totals = d_pub_tot;
+        ao.rp = d_rp_tab[nxt];
+        ao.rp0 = rp[nxt][0];
+        ao.tpos = trie_mode ? d_tpos_tab : nullptr;
+        ao.splane = d_splane_tab;
+        ao.rp_index = self_mode ? 0u : 1u;
+        ao.kcum = me.kcum; ao.cnt4 = cnt4; ao.nbp = nbp; ao.kshift = 2;
+        ao.width = d_totals;  // (levels of several tiles: the scan's grand total)
+        const bool merged = d > 1 || trie_mode;  // the union of several columns (a parsed stream is treated alike)
+        if (merged && nbp == 1) {  // a single tile evaluates the columns itself
+            ao.eval = 1; ao.kplane_w = me.kplane;
+        } else if (merged) {
+            hipLaunchKernelGGL((advance_reduce_kernel<P>), dim3(nbp), dim3(256), 0, st, x, sinfo, me.kplane, cnt4, nbp);
+            ao.kplane = me.kplane; ao.sinfo = sinfo;
+        } else {                   // one sample: the union trie is its trie, the expand kernel wrote planes and tile counts
+            ao.kplane = splane[0]; ao.kplane_w = me.kplane; ao.single = 1;
+            ao.kshift = 3;
+        }
+        const bool lean = !merged && nbp > 1 && keep_pw && !keep_slot && !stream_mode;   // advance_single_kernel takes the level
+        // One sample: the level's candidates are stored by the sweep itself.  Their number is known only after it: the records go
+        // to a block of their own arena, taken as large as the level could need and cut to size after the synchronisation.
+        if (lean && s.filtered && carena.cap) {
+            const size_t room = (carena.cap - carena.off) / sizeof(uint4);
+            s.crec_cap = (u32)(room < (size_t)F ? room : (size_t)F);
+        }
+        const bool fold = s.crec_cap > 0;
+        if (nbp > 1) {
+            // one sample: the tile counts from the planes its LF-step kernel wrote (that kernel added them up with four atomics per
+            // tile of 64 nodes before: 470 K memory-side atomics per launch of the wide levels); with them the candidates per tile
+            if (!merged) hipLaunchKernelGGL(lite_count_kernel, dim3((nbp + 63) / 64), dim3(256), 0, st, splane[0], (F + 63) >> 6, cntraw, nbp, 3u, fold ? 1u : 0u);
+            exclusive_scan<u32, u32>(merged ? cnt4 : cntraw, cnt4, (size_t)(fold ? 5 : 4) * nbp, scan_tmp, d_totals, st);
+        }
+        const bool fused_filter = s.filtered && nbp > 1;
+        if (fused_filter) {
+            ao.fa = filter_args(F, depth, w.order_mode); ao.candbits = me.cand_bits; ao.wsum = cand_wsum;
+            if (ao.single) ao.cand_copy = 1;  // (the level's LF-step kernel decided: the sweep only moves the words into place)
+            else ao.filter_on = 1;
+        }
+        if (fold) { ao.crec = reinterpret_cast<uint4*>(carena.base + carena.off); ao.crec_cap = s.crec_cap; }
+        if (nbp == 1) hipLaunchKernelGGL((advance_down_kernel<P>), dim3(1), dim3(256), 0, st, x, ao);
+        else if (lean) hipLaunchKernelGGL((advance_single_kernel<P>), dim3((nbp + 3) / 4), dim3(256), 0, st, x, ao);
+        else hipLaunchKernelGGL((advance_wave_kernel<P>), dim3(nbp), dim3(256), 0, st, x, ao);
+        if (s.filtered) {
+            if (int erc = emit_filter(me, F, depth, x, cur, w.order_mode, !fused_filter, fold)) return erc;
+        }
+        return 0;
+    }
+
+    // ---- publish: the last work of the level.  The owner answers its clients; with one sample the children's LF-step launch goes out
+    // now, sized on the device, assuming the level is of this level's frequency class (the largest frequency only falls with depth: a
+    // prefix changes class twice); then the host waits for the packet and catches up ----
+    int publish(Walk& w, Sweep& s) {
+        const u32 F = w.F, nbp = (F + TILE - 1) / TILE;
+        const int nxt = w.cur() ^ 1;
+        PublishArgs pa;
+        memset(&pa, 0, sizeof pa);
+        pa.total = nbp == 1 ? d_pub_tot : d_totals;  // new level's width: from the single tile, or the scan's total
+        pa.cmax_base = s.x.base; pa.cmax_bpr = s.x.bpr; pa.cmax_world = (u32)world;
+        if (s.filtered) pa.cand = d_totals64;
+        if (s.crec_cap) {  // the scan ran over the child counts and, behind them, the candidate counts: the width is what it had reached there
+            pa.total = cnt4 + (size_t)4 * nbp;
+            pa.grand = d_totals;
+            pa.cand = nullptr;
+        }
+        pa.clear = reinterpret_cast<u32*>(multi ? xsend : xrecv[nxt]);  // where the next level's expand reports its child maximum
+        pa.packet = reinterpret_cast<uint4*>(h_totals + 304); pa.seq = ++pub_seq;
+        pa.next = spec_mode ? d_dyn : nullptr;
+        pa.bc_header = owner_mode ? reinterpret_cast<uint4*>(bc_buf) : nullptr;
+        hipLaunchKernelGGL(publish_kernel, dim3(1), dim3(64), 0, st, pa);
+        if (owner_mode) {  // the union's child planes of this level follow the header: what a client needs to go on
+            const size_t bc_bytes = bcast_bytes(F);
+            DSM_HIP(hipMemcpyAsync(bc_buf + 16, w.L[w.depth].kplane, bc_bytes - 16, hipMemcpyDeviceToDevice, st));
+            w.owed.disarm();
+            if (prm.bcast(prm.owner_ctx, owner, bc_buf, bc_bytes, (void*)st)) return fail(DSM_E_SINK, "bcast callback failed");
+            stats.exchange_bytes_sent += bc_bytes * (u64)(world - 1);
+        }
+        if (spec_mode) { if (int rc = launch_lf(w, w.depth + 1, 0, w.w16, w.w9, s.slot, (u64)F * 4)) return rc; }
+        u32 pk[4];
+        if (int rc = wait_packet(pk)) return rc;
+        s.Fn = decode_level(pk[1], &s.w16, &s.w9);
+        // did the launch queued ahead run?  (the kernel tested the same two words the packet carries)
+        s.spec_hit = spec_mode && s.Fn > 0 && s.Fn <= level_cap(s.w16) && s.w16 == w.w16 && s.w9 == w.w9;
+        if (spec_mode && !s.spec_hit) --stats.expand_launches;  // (the launch queued ahead found no level, or another class, and did nothing)
+        h_totals[300] = pk[2]; h_totals[301] = pk[3];  // candidate totals of this level (read by emit_store)
+        if (int rc = check_width(s.Fn, s.w16)) return rc;
+        if (owner_mode) {  // what the clients do next: send the next level's columns and wait for its answer, or wait for the final verdict
+            if (!s.Fn) w.owed.arm(16);
+            else w.owed.arm_next((size_t)level_bytes(s.Fn, s.w16, s.w9), xrecv[nxt], bcast_bytes(s.Fn));
+        }
+        return 0;
+    }
+    // The publish kernel is the last work queued: its packet in pinned memory is the level's completion.  Spinning on it returns a
+    // few microseconds after the store; a stream synchronisation wakes the thread later.
+    int wait_packet(u32 pk[4]) {
+        volatile u32* fl = h_totals + 304;
+        u32 spins = 0;
+        while (*fl != pub_seq) {
+            if ((++spins & 0xFFFFu) == 0 && hipStreamQuery(st) != hipErrorNotReady) {  // finished (or failed) without the packet?
+                DSM_HIP(hipStreamSynchronize(st));
+                if (*fl != pub_seq) return fail(DSM_E_HIP, "publish kernel did not report");
+                break;
+            }
+            __builtin_ia32_pause();
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+        for (int q = 0; q < 4; ++q) pk[q] = fl[q];
+        return 0;
+    }
+
+    // ---- commit the children's level: the provisional window at its real size, the LF-step launch (unless the one queued ahead took
+    // the level), the reader-set orders of the children and, for a sub-prefix root, the order it had in the unsplit trie ----
+    int commit(Walk& w, const Sweep& s, LevelHost& child) {
+        const u32 F = w.F, Fn = s.Fn;
+        const int cur = w.cur(), nxt = cur ^ 1;
+        arena.off = s.mark;
+        child.n = Fn;
+        if (!Fn) return 0;
+        if (self_mode) child.slot = arena.get<u32>(Fn);     // same address as s.slot
+        if (!stream_mode) child.pw = arena.get<uint2>(Fn);  // the window's start, or right behind the links (256-byte granules, as the kernels assume)
+        if (int rc = alloc_kids(child)) return rc;
+        if (s.spec_hit) {
+            stats.expand_slots += Fn;
+            stats.expand_column_bytes += (u64)Fn * col_bytes(s.w16, s.w9);
+        } else {
+            if (int rc = launch_lf(w, w.depth + 1, Fn, s.w16, s.w9, child.slot)) return rc;
+        }
+        // orders are only needed by a rank that emits this prefix (and by the shallow pass that captures them)
+        const Kids kids = w.L[w.depth].kids();
+        if (!(w.o.emit || w.o.capture)) {}
+        else if (w.order_mode == 1)
+            hipLaunchKernelGGL((order_kernel<P>), grid_for(F), dim3(256), 0, st, F, s.x, nT[cur], order[cur], kids, order[nxt]);
+        else if (w.order_mode == 2 && d <= 64)
+            hipLaunchKernelGGL((order_big_kernel<P, 64>), grid_for(F, 64), dim3(64), 0, st, F, s.x, nT[cur], order16[cur], kids, order16[nxt]);
+        else if (w.order_mode == 2)
+            hipLaunchKernelGGL((order_big_kernel<P, 273>), grid_for(F, 64), dim3(64), 0, st, F, s.x, nT[cur], order16[cur], kids, order16[nxt]);
+        if (w.order_mode && w.o.seed && w.depth + 1 == w.o.seed->depth) {  // the sub-prefix root keeps its order from the unsplit trie
+            const std::vector<u16>& so = w.o.seed->ord[0];
+            if (int rc = upload_order(nxt, so.data(), so.size())) return rc;
+        }
+        return 0;
+    }
+
+    // ---- capture (the shallow pass of a split): the symbols and reader-set orders of the Fn children when they are at the captured
+    // depth.  The symbol comes from the links (slot), the sweep's (parent, flags) pairs (stream mode) or the path words (pw). ----
+    int capture_level(Walk& w, u32 Fn, const u32* slot, const uint2* pw) {
+        NodeOrder* cap = w.o.capture;
+        if (!Fn || !cap || w.depth + 1 != cap->depth) return 0;
+        const int nxt = w.cur() ^ 1;
+        const bool client = owner_mode && !is_owner;  // (a client keeps no reader counts or orders: which bases continue the prefix)
+        std::vector<u32> hs(Fn);
+        std::vector<u16> hn(Fn);
+        if (slot) DSM_HIP(hipMemcpyAsync(hs.data(), slot, (size_t)Fn * sizeof(u32), hipMemcpyDeviceToHost, st));
+        else if (stream_mode) {  // the symbol sits in the second word of the sweep's (parent, flags) pair
+            std::vector<uint2> hr(Fn);
+            DSM_HIP(hipMemcpyAsync(hr.data(), sa[nxt], (size_t)Fn * sizeof(uint2), hipMemcpyDeviceToHost, st));
+            DSM_HIP(hipStreamSynchronize(st));
+            for (u32 v = 0; v < Fn; ++v) hs[v] = hr[v].y & 3u;
+        } else {  // the last symbol of the node's path word
+            std::vector<uint2> hp(Fn);
+            DSM_HIP(hipMemcpyAsync(hp.data(), pw, (size_t)Fn * sizeof(uint2), hipMemcpyDeviceToHost, st));
+            DSM_HIP(hipStreamSynchronize(st));
+            for (u32 v = 0; v < Fn; ++v) hs[v] = (hp[v].y >> (2 * (w.depth % PW_CHUNK))) & 3u;
+        }
+        if (!client) DSM_HIP(hipMemcpyAsync(hn.data(), nT[nxt], (size_t)Fn * sizeof(u16), hipMemcpyDeviceToHost, st));
+        DSM_HIP(hipStreamSynchronize(st));
+        const u32 order_mode = client ? 0u : w.order_mode;
+        cap->sym.clear();
+        cap->ord.clear();
+        for (u32 v = 0; v < Fn; ++v) {
+            cap->sym.push_back(hs[v] & 3);
+            std::vector<u16> o(d == 1 || client ? 1 : hn[v]);  // (a single sample keeps no reader counts)
+            if (order_mode == 1) {
+                u64 ord = 0;
+                DSM_HIP(hipMemcpy(&ord, order[nxt] + v, sizeof(u64), hipMemcpyDeviceToHost));
+                for (u32 k = 0; k < hn[v]; ++k) o[k] = (u16)((ord >> (4 * k)) & 15);
+            } else if (order_mode == 2) {
+                DSM_HIP(hipMemcpy(o.data(), order16[nxt] + (size_t)v * d, (size_t)hn[v] * sizeof(u16), hipMemcpyDeviceToHost));
+            }
+            cap->ord.push_back(o);
+        }
+        return 0;
+    }
+
+    // the level is done: its width in the stats (and on stderr)
+    void count_level(const Walk& w) {
+        if (w.trace) {
+            if (owner_mode && !is_owner) fprintf(stderr, "dsm level prefix=%s depth=%u F=%u (client of rank %d)\n", w.prefix.c_str(), w.depth, w.F, owner);
+            else fprintf(stderr, "dsm level prefix=%s depth=%u F=%u\n", w.prefix.c_str(), w.depth, w.F);
+        }
+        stats.union_nodes += w.depth >= 1 ? w.F : 0;
+        if (w.F > stats.max_frontier) stats.max_frontier = w.F;
+        ++stats.levels;
+    }
+    // on to the children's level: Fn nodes of class (w16, w9)
+    void step(Walk& w, u32 Fn, bool w16, bool w9) {
+        w.F = Fn;
+        ++w.depth;
+        w.w16 = w16;
+        w.w9 = w9;
+    }
+
+    // ---- the end of a prefix: its tuples or wire stream, and the verdict on the emission side every rank must share ----
+    int finish_prefix(Walk& w, dsm_tuple_sink tsink, dsm_byte_sink bsink, void* ctx) {
+        const u32 nlev = (u32)w.L.size();  // levels 0..nlev-1, level l holds the nodes of depth l
+        if (stream_mode) {
+            if (w.o.emit) { if (int rc = finish_stream(w.L, nlev, bsink, ctx)) return rc; }
+            return 0;
+        }
+        bool ready = false;
+        if (w.emitting) {
+            int rc = finish_mine(w.L, nlev, tsink, ctx, &ready);
+            if (rc == DSM_E_CAPACITY && multi) { w.emit_failed = true; ready = false; }
+            else if (rc) return rc;
+        }
+        if (owner_mode) {  // only the owner emits: its word on the emission side reaches the clients with one last broadcast
+            u32 hdr[4] = {w.emit_failed ? BC_CAPACITY : BC_OK, 0, 0, 0};
+            if (is_owner) {
+                DSM_HIP(hipMemcpyAsync(bc_buf, hdr, 16, hipMemcpyHostToDevice, st));
+                DSM_HIP(hipStreamSynchronize(st));
+            }
+            w.owed.disarm();
+            if (prm.bcast(prm.owner_ctx, owner, bc_buf, 16, (void*)st)) return fail(DSM_E_SINK, "bcast callback failed");
+            if (!is_owner) {
+                DSM_HIP(hipMemcpyAsync(hdr, bc_buf, 16, hipMemcpyDeviceToHost, st));
+                DSM_HIP(hipStreamSynchronize(st));
+            }
+            if (hdr[0] == BC_ABORT) return fail(DSM_E_SINK, "the prefix's owner failed and aborted the prefix (its own error says why)");
+            if (hdr[0] != BC_OK) return fail(DSM_E_CAPACITY, "device arena exhausted on the prefix's owner: use a longer prefix or a larger arena_bytes");
+        } else if (multi) {  // every rank learns whether some rank's emission side overflowed: split together or not at all
+            u64 ok = w.emit_failed ? 0 : 1, all_ok = 0;
+            if (int rc = agree_min(ok, &all_ok)) return rc;
+            if (!all_ok) return fail(DSM_E_CAPACITY, "device arena exhausted on a rank: use a longer prefix or a larger arena_bytes");
+        }
+        if (ready) pend.submit = true;   // (the set is prepared; flush_pending hands it over once the next prefix is under way)
+        else pend.E = nullptr;
+        return 0;
+    }
+
+    // ---- the run's device time, LF-step time and counters ----
+    int read_back(const Walk& w) {
+        DSM_HIP(hipEventRecord(ev1, st));
+        timeline("finish queued", w.prefix.c_str());
+        DSM_HIP(hipStreamSynchronize(st));
+        timeline("device done", w.prefix.c_str());
         float ms = 0;
         DSM_HIP(hipEventElapsedTime(&ms, ev0, ev1));
         stats.device_ms += ms;
         float expand_ms = 0;
-        for (size_t k = 0; k + 1 < nev; k += 2) {
+        for (size_t k = 0; k + 1 < w.nev; k += 2) {
             float t = 0;
             DSM_HIP(hipEventElapsedTime(&t, evpool[k], evpool[k + 1]));
             expand_ms += t;
@@ -3494,25 +3564,36 @@ struct MinerT : MinerBase {
     // only if capacities agree, so ranks must use equal arena sizes.  (`reported` counts every node once: a run counts the depths it
     // emits, the shallow pass none; union_nodes and the cost counters still count the enforced path
     // once per sub-run in that case.)
-    typedef typename Engine<P>::NodeOrder NodeOrder;
-    int run_auto(const std::string& prefix, dsm_tuple_sink ts, void* ctx, bool emit, u32 lo, const NodeOrder* seed) {
-        int rc = e.run(prefix.c_str(), ts, nullptr, ctx, emit, lo, ~0u, ~0u, seed);
+    // o: whether to emit, the shallowest depth emitted (emit_lo) and the seed; the rest of it stays at the defaults
+    int run_auto(const std::string& prefix, dsm_tuple_sink ts, void* ctx, const RunOpts& o) {
+        int rc = e.run(prefix.c_str(), ts, nullptr, ctx, o);
         if (rc != DSM_E_CAPACITY || prefix.size() >= 32) return rc;
         ++e.splits;
         if (getenv("DSM_TRACE_SPLITS")) fprintf(stderr, "dsm split rank=%d prefix=%s Fcap=%u: %s\n", e.rank, prefix.c_str(), e.Fcap, dsm_last_error());
         const u32 k = (u32)prefix.size();
         NodeOrder cap;  // shallow pass: the children of the prefix node with all four siblings visible -> their orders
         cap.depth = k + 1;
-        rc = e.run(prefix.c_str(), ts, nullptr, ctx, false, lo, ~0u, k + 1, seed, &cap, false);
+        RunOpts shallow = o;
+        shallow.emit = false;
+        shallow.expand_cap = k + 1;
+        shallow.capture = &cap;
+        shallow.count = false;
+        rc = e.run(prefix.c_str(), ts, nullptr, ctx, shallow);
         if (rc) return rc;
         for (size_t q = 0; q < cap.sym.size(); ++q) {
             NodeOrder sub;
             sub.depth = k + 1;
             sub.ord.push_back(cap.ord[q]);
-            rc = run_auto(prefix + "ACGT"[cap.sym[q]], ts, ctx, emit, k + 1, &sub);
+            RunOpts below = o;
+            below.emit_lo = k + 1;
+            below.seed = &sub;
+            rc = run_auto(prefix + "ACGT"[cap.sym[q]], ts, ctx, below);
             if (rc) return rc;
         }
-        return e.run(prefix.c_str(), ts, nullptr, ctx, emit, lo, k, k + 1, seed);
+        RunOpts top = o;  // the prefix node and its ancestors
+        top.emit_hi = k;
+        top.expand_cap = k + 1;
+        return e.run(prefix.c_str(), ts, nullptr, ctx, top);
     }
     // The wire stream of a prefix whose trie does not fit the device buffers, as the concatenation of slices of its sub-prefixes'
     // streams.  With p = p1..pk and c1 < .. < cm the bases that continue p,
@@ -3526,7 +3607,7 @@ struct MinerT : MinerBase {
         const u32 k = (u32)prefix.size();
         e.stream_rbase = rbase; e.stream_head_skip = head_skip; e.stream_tail_levels = tail_levels; e.stream_last = last;
         const u64 before = e.stats.reported;
-        int rc = e.run(prefix.c_str(), nullptr, nullptr, ctx, true);
+        int rc = e.run(prefix.c_str(), nullptr, nullptr, ctx);
         if (rc != DSM_E_CAPACITY || k >= 32) {
             const u64 rep = e.stats.reported - before;            // the enforced path's k nodes and everything below p's node
             if (below) *below = rep >= k ? rep - k + (k ? 1 : 0) : 0;  // (the root of the empty prefix is not a node of the stream)
@@ -3536,7 +3617,11 @@ struct MinerT : MinerBase {
         if (getenv("DSM_TRACE_SPLITS")) fprintf(stderr, "dsm split rank=%d prefix=%s Fcap=%u: %s\n", e.rank, prefix.c_str(), e.Fcap, dsm_last_error());
         NodeOrder cap;  // shallow pass: which bases continue p
         cap.depth = k + 1;
-        rc = e.run(prefix.c_str(), nullptr, nullptr, ctx, false, 1, ~0u, k + 1, nullptr, &cap);
+        RunOpts shallow;
+        shallow.emit = false;
+        shallow.expand_cap = k + 1;
+        shallow.capture = &cap;
+        rc = e.run(prefix.c_str(), nullptr, nullptr, ctx, shallow);
         if (rc) return rc;
         u64 sum = 0;
         const size_t m = cap.sym.size();
@@ -3564,7 +3649,11 @@ struct MinerT : MinerBase {
             const bool mine = e.owner_mode ? e.is_owner : (!e.prm.emit_owner_only || e.world <= 1 || (k % e.world) == e.rank);
             e.stream_tag = k;
             if (e.stream_mode) rc = stream_auto(prefixes[k] ? prefixes[k] : "", ctx, 0, 0, 0, true, nullptr);
-            else rc = run_auto(prefixes[k] ? prefixes[k] : "", ts, ctx, mine, 1, nullptr);
+            else {
+                RunOpts o;
+                o.emit = mine;
+                rc = run_auto(prefixes[k] ? prefixes[k] : "", ts, ctx, o);
+            }
         }
         int rc2 = e.finish_emits();
         if (e.stream_mode) {  // the last prefixes may still be on their way to the sink
@@ -3607,8 +3696,6 @@ static int merge_impl(dsm_trie* const* tr, int n, const dsm_params* p, dsm_tuple
     return m->run("", sink, nullptr, ctx, stats);
 }
 
-// one engine run over the given tries (sample id = position): capture (shallow pass, nothing emitted), a unit (run_auto: a unit that
-// does not fit the buffers splits like any prefix) or the closing pass over the depths lo..hi
 // An engine a server keeps: created for tries of up to `cap` nodes each (place holders size its buffers) and pointed at the tries of
 // every run that fits; a run that does not fit gets a new, larger one.  (Creating an engine costs ~50 ms of allocations; a server
 // runs dozens of small passes over the tops of its streams and one pass per unit.)
@@ -3618,8 +3705,8 @@ struct KeptEngine {
     u64 cap = 0;
 };
 template <typename P>
-static int server_run_t(dsm_trie* const* tr, int n, const dsm_params& q, const std::string& prefix, dsm_tuple_sink sink, void* ctx, bool emit,
-                        u32 lo, u32 hi, u32 expand_cap, const ServerOrder* seed, ServerOrder* capture, dsm_stats* out, KeptEngine<P>* keep, u64 min_cap) {
+static int server_run_t(dsm_trie* const* tr, int n, const dsm_params& q, const std::string& prefix, dsm_tuple_sink sink, void* ctx, const RunOpts& o,
+                        dsm_stats* out, KeptEngine<P>* keep, u64 min_cap) {
     std::unique_ptr<MinerT<P>> own;
     MinerT<P>* m = nullptr;
     u64 need = 0;
@@ -3648,14 +3735,10 @@ static int server_run_t(dsm_trie* const* tr, int n, const dsm_params& q, const s
     }
     if (keep)
         for (int k = 0; k < n; ++k) m->e.tries[k] = tr[k];
-    typename Engine<P>::NodeOrder sd, cp;
-    if (seed) { sd.depth = seed->depth; sd.sym = seed->sym; sd.ord = seed->ord; }
-    if (capture) cp.depth = capture->depth;
     int rc;
-    if (capture || hi != ~0u) rc = m->e.run(prefix.c_str(), sink, nullptr, ctx, emit, lo, hi, expand_cap, seed ? &sd : nullptr, capture ? &cp : nullptr, capture == nullptr);
-    else rc = m->run_auto(prefix, sink, ctx, emit, lo, seed ? &sd : nullptr);
+    if (o.capture || o.emit_hi != ~0u) rc = m->e.run(prefix.c_str(), sink, nullptr, ctx, o);
+    else rc = m->run_auto(prefix, sink, ctx, o);
     const int rc2 = m->e.finish_emits();
-    if (capture) { capture->sym = cp.sym; capture->ord = cp.ord; }
     if (out) *out = m->e.stats;
     return rc ? rc : rc2;
 }
@@ -3665,10 +3748,10 @@ struct ServerEngines {  // for the passes over the tops of the streams (top) and
 };
 // which: 0 = an engine for this run only, 1 = the kept engine for tops, 2 = the kept engine for units
 int server_run(bool wide, dsm_trie* const* tr, int n, const dsm_params& q, const std::string& prefix, dsm_tuple_sink sink, void* ctx,
-               bool emit, u32 lo, u32 hi, u32 expand_cap, const ServerOrder* seed, ServerOrder* capture, dsm_stats* out, ServerEngines* keep, int which) {
+               const RunOpts& o, dsm_stats* out, ServerEngines* keep, int which) {
     const u64 min_cap = which == 1 ? 65536 : (1u << 20);
-    if (wide) return server_run_t<u64>(tr, n, q, prefix, sink, ctx, emit, lo, hi, expand_cap, seed, capture, out, !keep || !which ? nullptr : (which == 1 ? &keep->top64 : &keep->unit64), min_cap);
-    return server_run_t<u32>(tr, n, q, prefix, sink, ctx, emit, lo, hi, expand_cap, seed, capture, out, !keep || !which ? nullptr : (which == 1 ? &keep->top32 : &keep->unit32), min_cap);
+    if (wide) return server_run_t<u64>(tr, n, q, prefix, sink, ctx, o, out, !keep || !which ? nullptr : (which == 1 ? &keep->top64 : &keep->unit64), min_cap);
+    return server_run_t<u32>(tr, n, q, prefix, sink, ctx, o, out, !keep || !which ? nullptr : (which == 1 ? &keep->top32 : &keep->unit32), min_cap);
 }
 
 // ---- what the C entry points (abi.hip) and the server side (server.hip) use of the engine: engine_api.h -------------------------------

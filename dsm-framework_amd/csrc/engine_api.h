@@ -32,19 +32,32 @@ int mine_once(dsm_index* const* idx, int n, const dsm_params* p, dsm_tuple_sink 
 int enumerate_once(const dsm_index* idx, const char* prefix, u32 fmin, u32 maxdepth, dsm_byte_sink sink, void* ctx, dsm_stats* stats);
 int merge_once(bool wide, dsm_trie* const* tr, int n, const dsm_params* p, dsm_tuple_sink sink, void* ctx, dsm_stats* stats);
 
-// ---- the server side's engine runs (dsm_server, server.hip) ----
-struct ServerOrder {  // Engine<P>::NodeOrder without the position type
+// ---- how one engine run (Engine<P>::run) cuts a prefix's trie ----
+// Used when a prefix is split because a level did not fit (MinerT::run_auto) and by the server side's passes.  Reader-set iteration
+// orders depend on the whole sibling structure above a node, so a sub-prefix run must start from the order its root had in the
+// unsplit trie (seed), captured by the shallow pass of the parent (capture).
+struct NodeOrder {
     u32 depth = 0;
-    std::vector<u32> sym;
-    std::vector<std::vector<u16>> ord;
+    std::vector<u32> sym;               // capture: symbol of each node at `depth`
+    std::vector<std::vector<u16>> ord;  // capture: their orders; seed: ord[0]
 };
+struct RunOpts {
+    bool emit = true;                  // this rank emits the prefix (tuples, or the wire stream)
+    u32 emit_lo = 1, emit_hi = ~0u;    // only nodes with emit_lo <= depth <= emit_hi are filtered and emitted
+    u32 expand_cap = ~0u;              // nodes at this depth or deeper are not expanded
+    const NodeOrder* seed = nullptr;   // the order of the node at seed->depth
+    NodeOrder* capture = nullptr;      // receives the symbols and orders of the nodes at capture->depth
+    bool count = true;                 // `reported` counts the nodes of the depths emit_lo..emit_hi (not in a shallow pass)
+};
+
+// ---- the server side's engine runs (dsm_server, server.hip) ----
 struct ServerEngines;  // the engines a server keeps between its runs (engine.hip)
 ServerEngines* server_engines_create();
 void server_engines_destroy(ServerEngines* e);
-// One engine run over the given tries (sample id = position): capture (shallow pass, nothing emitted), a unit (a unit that does not fit
-// the buffers splits like any prefix) or the closing pass over the depths lo..hi.  which: 0 = an engine for this run only, 1 = the kept
-// engine for the passes over the tops of the streams, 2 = the kept engine for units.
-int server_run(bool wide, dsm_trie* const* tr, int n, const dsm_params& q, const std::string& prefix, dsm_tuple_sink sink, void* ctx, bool emit, u32 lo,
-               u32 hi, u32 expand_cap, const ServerOrder* seed, ServerOrder* capture, dsm_stats* out, ServerEngines* keep = nullptr, int which = 0);
+// One engine run over the given tries (sample id = position): capture (shallow pass, o.capture), a unit (o.emit_hi open: a unit that does
+// not fit the buffers splits like any prefix) or the closing pass over the depths o.emit_lo..o.emit_hi.  which: 0 = an engine for this
+// run only, 1 = the kept engine for the passes over the tops of the streams, 2 = the kept engine for units.
+int server_run(bool wide, dsm_trie* const* tr, int n, const dsm_params& q, const std::string& prefix, dsm_tuple_sink sink, void* ctx,
+               const RunOpts& o, dsm_stats* out, ServerEngines* keep = nullptr, int which = 0);
 
 }  // namespace dsm

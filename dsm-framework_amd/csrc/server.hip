@@ -473,17 +473,21 @@ struct dsm_server {
         auto f = orders.find(path);
         if (f != orders.end()) { *out = f->second; return 0; }
         const std::vector<u8> parent(path.begin(), path.end() - 1);
-        ServerOrder cap, seed;
+        NodeOrder cap, seed;
         cap.depth = (u32)K + (u32)path.size();
-        const ServerOrder* sp = nullptr;
+        RunOpts o;  // a shallow pass over the parent's children: their orders
+        o.emit = false;
+        o.expand_cap = cap.depth;
+        o.capture = &cap;
+        o.count = false;
         if (!parent.empty()) {
             std::vector<u16> po;
             if (int r = order_of(parent, hol, wide, chain, &po)) return r;
             seed.depth = (u32)K + (u32)parent.size();
             seed.ord.push_back(po);
-            sp = &seed;
+            o.seed = &seed;
         }
-        if (int r = server_run(wide, hol, d, prm, chain + text_of(parent), sink, ctx, false, 1, ~0u, cap.depth, sp, &cap, nullptr, engines, 1)) return r;
+        if (int r = server_run(wide, hol, d, prm, chain + text_of(parent), sink, ctx, o, nullptr, engines, 1)) return r;
         size_t q = 0;
         while (q < cap.sym.size() && cap.sym[q] != (u32)path.back()) ++q;
         if (q == cap.sym.size()) return fail(DSM_E_HIP, "dsm_server: the shallow pass did not find the node " + chain + text_of(path));
@@ -527,18 +531,23 @@ struct dsm_server {
         const u32 depth = (u32)full.size();
         dsm_stats a;
         memset(&a, 0, sizeof a);
-        ServerOrder seed;
+        NodeOrder seed;
         seed.depth = depth;
         seed.ord.emplace_back();
         r = order_of(path, hol.data(), wide, chain, &seed.ord[0]);
+        RunOpts o;
+        o.seed = &seed;
         if (!r && is_unit) {
             // (small units share one engine, whose buffers then stay; a large unit gets an engine of its size that goes with it)
             u64 biggest = 0;
             for (auto* t : unit) biggest = t->nodes > biggest ? t->nodes : biggest;
-            r = server_run(wide, unit.data(), d, prm, full, sink, ctx, true, U, ~0u, ~0u, &seed, nullptr, &a, engines, biggest <= (1u << 25) ? 2 : 0);
+            o.emit_lo = U;
+            r = server_run(wide, unit.data(), d, prm, full, sink, ctx, o, &a, engines, biggest <= (1u << 25) ? 2 : 0);
             if (!r) { add_stats(a, a.union_nodes >= (u64)(U - 1) ? a.union_nodes - (u64)(U - 1) : 0); ++units_merged; if (nodes > peak_unit_nodes) peak_unit_nodes = nodes; }
         } else if (!r) {
-            r = server_run(wide, hol.data(), d, prm, full, sink, ctx, true, depth, depth, depth + 1, &seed, nullptr, &a, engines, 1);
+            o.emit_lo = o.emit_hi = depth;  // the node's depth only, its children shown
+            o.expand_cap = depth + 1;
+            r = server_run(wide, hol.data(), d, prm, full, sink, ctx, o, &a, engines, 1);
             if (!r) add_stats(a, 1);
         }
         cleanup();
@@ -563,7 +572,10 @@ struct dsm_server {
         dsm_stats a;
         memset(&a, 0, sizeof a);
         if (!r && !chain.empty()) {
-            r = server_run(wide, hol.data(), d, prm, chain, sink, ctx, true, 1, (u32)K, (u32)K + 1, nullptr, nullptr, &a, engines, 1);
+            RunOpts o;  // the depths 1..K
+            o.emit_hi = (u32)K;
+            o.expand_cap = (u32)K + 1;
+            r = server_run(wide, hol.data(), d, prm, chain, sink, ctx, o, &a, engines, 1);
             if (!r) add_stats(a, (u64)K);
         }
         for (auto* t : hol) if (t) dsm_trie_free(t);
