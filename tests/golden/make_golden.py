@@ -9,7 +9,8 @@ raw client byte streams captured with a TCP sink, and metaserver stdout.
     python tests/golden/make_golden.py            # regenerates everything
 
 Fixture sets (see tests/golden/MANIFEST.json, written by this script):
-  toy3   3 samples x 1000 reads x 50 bp, 6.6 kbp genome (order-6 de Bruijn + random); fmin 2; prefixes A C G T and AC GT TTG
+  toy3   3 samples x 1000 reads x 50 bp, 6.6 kbp genome (order-6 de Bruijn + random); fmin 2; prefixes A C G T and AC GT TTG;
+         server configurations ent_exact / ent_ulp put -e and -E on tuple entropies and one ulp inside them
   toyN   1 sample with N / lower-case / IUPAC symbols (normalisation + 7-symbol alphabet)
   deep1  toy3 sample 1, --fmin 1 -M 40 (followOneBranch path), prefixes A C G T
   many30 30 tiny samples, --fmin 3 -M 14 (more than 13 readers: std::unordered_set rehashes, ids share buckets)
@@ -17,6 +18,7 @@ Fixture sets (see tests/golden/MANIFEST.json, written by this script):
 """
 import gzip
 import json
+import math
 import os
 import shutil
 import socket
@@ -167,6 +169,16 @@ def run_servers(names, fmis, prefixes, client_args, server_args):
     return outs
 
 
+def exact_thresholds(d, outs):
+    """(lo, hi): two entropies of printed tuples whose double changes when the frequencies are summed in id order instead of the
+    print order (tests/entlib.py): the largest below 2.0 and the median of the rest"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import entlib
+    ents = sorted({entlib.exact_entropy(d, ln.freqs) for o in outs for ln in entlib.parse(o) if entlib.order_sensitive(d, ln)})
+    ents = [e for e in ents if e < 2.0]
+    return ents[(len(ents) - 1) // 2], ents[-1]
+
+
 def put(path, data):
     os.makedirs(os.path.dirname(path), exist_ok=True)
     if path.endswith(".gz"):
@@ -212,12 +224,26 @@ def main():
         "emin_m": ["-E", "1.4", "-e", "0.5", "-m", "8"],
         "noent": ["-E", "0", "-P", "1"],
     }
+    toy_outs = {}
     for cfg, sargs in server_cfgs.items():
         # -P 1 variants are safe; pmin>1 needs every depth<=6 node in >=2 samples
         outs = run_servers(names, fmis, prefixes + (["AC", "GT"] if cfg != "default" else ["AC", "GT", "TTG"]),
                            ["--fmin", "2"], sargs)
         for p, d in outs.items():
             put(os.path.join(HERE, "toy3", "server.%s.%s.txt.gz" % (cfg, p)), d)
+        toy_outs[cfg] = outs
+    # thresholds ON tuple entropies (metaserver parses them with atof; %.17g round-trips a double): the range is closed, so the
+    # tuples at either end are printed with ent_exact and dropped with ent_ulp, whose ends lie one ulp inside
+    lo, hi = exact_thresholds(len(names), [toy_outs["default"][p] for p in prefixes + ["AC", "GT"]])
+    exact_cfgs = {
+        "ent_exact": ["-E", "%.17g" % hi, "-e", "%.17g" % lo],
+        "ent_ulp": ["-E", "%.17g" % math.nextafter(hi, -math.inf), "-e", "%.17g" % math.nextafter(lo, math.inf)],
+    }
+    for cfg, sargs in exact_cfgs.items():
+        outs = run_servers(names, fmis, prefixes + ["AC", "GT"], ["--fmin", "2"], sargs)
+        for p, d in outs.items():
+            put(os.path.join(HERE, "toy3", "server.%s.%s.txt.gz" % (cfg, p)), d)
+    server_cfgs.update(exact_cfgs)
     manifest["sets"]["toy3"] = {"names": names, "fmin": 2, "prefixes": prefixes + deep_prefixes,
                                 "server_cfgs": server_cfgs,
                                 "stream_bytes": {"%s/%s" % k: v for k, v in streams.items()}}
@@ -294,7 +320,13 @@ def main():
     manifest["sets"]["many30"] = {"names": names30, "fmin": 3, "maxdepth": 14, "prefixes": ["AC", "G"], "server_cfgs": cfgs30}
 
     manifest["glibc"] = os.confstr("CS_GNU_LIBC_VERSION")
-    with open(os.path.join(HERE, "MANIFEST.json"), "w") as f:
+    mpath = os.path.join(HERE, "MANIFEST.json")
+    if os.path.exists(mpath):  # keep the case table make_golden_distmat.py wrote
+        with open(mpath) as f:
+            old = json.load(f)
+        if "distmat" in old:
+            manifest["distmat"] = old["distmat"]
+    with open(mpath, "w") as f:
         json.dump(manifest, f, indent=1, sort_keys=True)
     shutil.rmtree(work)
     total = 0

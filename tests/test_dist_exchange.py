@@ -1,5 +1,6 @@
 """N>1 path, host side: the per-level all-gather plumbing with 2 gloo ranks on CPU (layout, halves, errors),
 and -- on the GPU box -- two ranks sharing the one GPU, each owning one sample, against the reference golden."""
+import math
 import os
 import socket
 import sys
@@ -147,6 +148,67 @@ def test_one_sample_per_rank_matches_reference_server(golden, setname, world, cf
     for p in prefixes:
         want = sum(ix.enumerate(n, p, fmin=m["fmin"], maxdepth=m.get("maxdepth", 0xFFFFFFFF))[1][0] for ix, n in zip(oidx, names))
         assert sum(reported[p]) == want
+
+
+def _crafted_worker(rank, world, port, q, fmis, settings):
+    sys.path.insert(0, os.path.join(ROOT, "dsm-framework_amd"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    _init(rank, world, port)
+    import entlib
+    import pydsm
+    from pydsm.dist import Exchange
+    torch.cuda.set_device(0)
+    ex = Exchange(1 << 22, world, "cuda:0")
+    idx = [pydsm.Index(fmis[rank], device=0)]
+    out = []
+    for emin, emax in settings:
+        with pydsm.Miner(idx, world_size=world, rank=rank, allgather=ex.allgather, exchange=ex.params(), emin=emin, emax=emax,
+                         **entlib.CRAFT_KW) as m:
+            text, st = m.mine("A")
+            out.append((text, st.reported, st.union_nodes, st.tuples, st.pairs, st.pair_order_exact))
+    q.put((rank, out, ex.calls))
+    idx[0].close()
+    dist.destroy_process_group()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("f", [512, 65535])
+def test_width_class_crossing_in_one_rank(tmp_path, f):
+    """One sample per rank, crafted runs of A (tests/entlib.py): rank 0 holds the node A^8 f times, the other ranks fewer, so only
+    rank 0's largest child frequency of that level reaches the next width class (512: no packed 16-bit words; 65535: no u16 columns).
+    publish_kernel ORs the class over the ranks and it travels in the publish packet: every rank must decode the level alike."""
+    import entlib
+    import orc
+    targets = entlib.freq_targets(3, f)
+    fmis = entlib.build_crafted(str(tmp_path), "x%d" % f, targets)
+    names = [entlib.sample_name(p) for p in fmis]
+    oidx = [orc.Index(p) for p in fmis]
+    unf, _ = orc.mine(oidx, names, ["A"], emax=0.0, **entlib.CRAFT_KW)
+    lines = entlib.parse(unf)
+    e = entlib.exact_entropy(3, entlib.boundary_line(lines, targets).freqs)
+    settings = [(0.0, 0.0), (e, entlib.BIG), (math.nextafter(e, math.inf), entlib.BIG)]
+    wants = [entlib.restate(lines, 3, emin, emax) for emin, emax in settings]
+    assert len({w[1] for w in wants}) == 3  # the boundary tuple is printed, then dropped
+    client = [ix.enumerate(n, "A", fmin=entlib.CRAFT_KW["fmin"], maxdepth=entlib.CRAFT_KW["maxdepth"])[1][0] for ix, n in zip(oidx, names)]
+    for ix in oidx:
+        ix.close()
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    ps = [ctx.Process(target=_crafted_worker, args=(r, 3, port, q, fmis, settings)) for r in range(3)]
+    for p in ps:
+        p.start()
+    res = sorted(q.get(timeout=300) for _ in ps)
+    for p in ps:
+        p.join(60)
+    unions = set()
+    for rank, out, calls in res:
+        assert calls > 0 and len(out) == len(settings)
+        for (emin, emax), (want, nt, npairs), (text, rep, union, tuples, pairs, exact) in zip(settings, wants, out):
+            assert text == want and (tuples, pairs) == (nt, npairs) and exact == 1, (rank, emin.hex())
+            assert rep == client[rank], rank  # a rank reports its own sample's nodes
+            unions.add(union)
+    assert len(unions) == 1  # the same union trie on every rank
 
 
 def _owner_worker(rank, world, port, q, fmis, prefixes, kw, arena):
