@@ -1133,17 +1133,18 @@ __global__ __launch_bounds__(256) void down_kernel(u32 F, const T* __restrict__ 
     }
 }
 
-// candidate k of a level gets its post-order rank among all candidates of the prefix; the tuple's sizes go to their place
-// in output order (the ranks of neighbouring candidates are far apart: the levels are in colex order, the output in trie order)
+// candidate k of a level gets its post-order rank among all candidates of the prefix; the tuple's sizes and where it came from (its
+// index in the level: the level itself is its path length) go to their place in output order (the ranks of neighbouring candidates are
+// far apart: the levels are in colex order, the output in trie order)
 // (crec: the records the advance sweep of a single sample stored -- node, 0, frequency -- instead of the four arrays: one pair each)
 __global__ void cand_rank_kernel(u32 ncand, const u32* __restrict__ cand_node, const u32* __restrict__ cand_poff, u32 npairs,
-                                 const u32* __restrict__ start, const u32* __restrict__ sub, u32 level, u32* __restrict__ crank,
+                                 const u32* __restrict__ start, const u32* __restrict__ sub, u32 level, u32* __restrict__ src,
                                  u32* __restrict__ plen, u32* __restrict__ npair, const uint4* __restrict__ crec) {
     u32 k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= ncand) return;
     u32 v = crec ? crec[k].x : cand_node[k];
     u32 r = start[v] + sub[v] - 1;
-    crank[k] = r;
+    src[r] = k;
     plen[r] = level;
     npair[r] = crec ? 1u : (k + 1 < ncand ? cand_poff[k + 1] : npairs) - cand_poff[k];
 }
@@ -1153,15 +1154,11 @@ struct LevelDev {
     const u32* cand_node;
     const u32* cand_poff;
     const uint4* crec;  // (one sample, stored by the advance sweep: {node, 0, frequency} per candidate instead of the arrays around it)
-    const u32* crank;   // post-order rank of candidate k
     const u32* ids;
     const u64* freqs;
-    u32 ncand;
-    u32 npairs;
-    u32 cbase;          // candidates of the shallower levels
 };
 
-// offsets of the chunk boundaries (path bytes, pairs) for the host: out[2c], out[2c+1] for boundary tuple tb[c]
+// offsets of the chunk boundaries (path bytes, pairs): out[2c], out[2c+1] for boundary tuple tb[c] (read by the fills and, copied, by the host)
 constexpr int EMIT_MAX_CHUNKS = 8;
 struct ChunkBounds { u32 tb[EMIT_MAX_CHUNKS + 1]; int n; };
 __global__ void chunk_bounds_kernel(ChunkBounds cbs, const u32* __restrict__ path_off, const u32* __restrict__ pair_off, u32* __restrict__ out) {
@@ -1169,8 +1166,10 @@ __global__ void chunk_bounds_kernel(ChunkBounds cbs, const u32* __restrict__ pat
     if (c <= cbs.n) { out[2 * c] = path_off[cbs.tb[c]]; out[2 * c + 1] = pair_off[cbs.tb[c]]; }
 }
 
-// Paths and pairs of all tuples.  Threads take the candidates level by level in node order.  A path is put together from the path
-// words of the node and of its ancestors at the chunk boundaries (levels 16, 32, ...): 16 symbols per dependent load.
+// Paths and pairs of the tuples of one chunk of output ranks.  Thread r fills the tuple of rank r: its level is its path length, its
+// candidate index in that level src[r] (cand_rank_kernel), so neighbouring lanes write neighbouring path bytes, pairs and verdicts.
+// A path is put together from the path words of the node and of its ancestors at the chunk boundaries (levels 16, 32, ...): 16 symbols
+// per dependent load.
 // What the host emitter used to compute per tuple (emit_job's first pass, 3.4 ms of sixteen threads per chunk of four million tuples,
 // in the open at the end of a pass): the exact entropy (metaserver.cpp:366-389 from the uploaded tables: the same entries added in the
 // same order, one division, one subtraction -- IEEE double, bit-identical to the host's), the emin / emax verdict (:413) and the offsets
@@ -1185,50 +1184,43 @@ struct FillVerdict {
     u32* counts;          // of the chunk: [0] dropped, [1] left to the host
     const double* terms;  // device copies of term_table() / logn_table()
     const double* logn;
+    const u32* bounds;    // chunk_bounds_kernel's output: the chunk starts at path byte bounds[2 * chunk], pair bounds[2 * chunk + 1]
     u32 chunk, d;
-    u32 pb0, qb0;         // path byte / pair at which the chunk starts
     double emin, emax;
 };
-__global__ __launch_bounds__(256) void tuple_fill_kernel(u32 nt, u32 nlev, const LevelDev* __restrict__ lv, const u32* __restrict__ path_off,
-                                                         const u32* __restrict__ pair_off, char* __restrict__ paths, u32* __restrict__ ids,
-                                                         u64* __restrict__ freqs, u32 rank_lo, u32 rank_hi, FillVerdict fv) {
-    // the per-level arrays and candidate bases are read by every walk: kept in LDS, with the text of every byte of four symbols
+// ids null: no id array (one sample, every id 0)
+__global__ __launch_bounds__(256) void tuple_fill_kernel(u32 nlev, const LevelDev* __restrict__ lv, const u32* __restrict__ path_off,
+                                                         const u32* __restrict__ pair_off, const u32* __restrict__ src, char* __restrict__ paths,
+                                                         u32* __restrict__ ids, u64* __restrict__ freqs, u32 rank_lo, u32 rank_hi, FillVerdict fv) {
+    // the levels' path-word arrays are read by every walk: kept in LDS, with the text of every byte of four symbols
     constexpr u32 LDS_LEVELS = 1024;
     __shared__ const uint2* s_pw[LDS_LEVELS];
-    __shared__ u32 s_cbase[LDS_LEVELS];
     __shared__ u32 s_text[256];
     const u32 nl = nlev < LDS_LEVELS ? nlev : LDS_LEVELS;
-    for (u32 q = threadIdx.x; q < nl; q += blockDim.x) { s_pw[q] = lv[q].pw; s_cbase[q] = lv[q].cbase; }
+    for (u32 q = threadIdx.x; q < nl; q += blockDim.x) s_pw[q] = lv[q].pw;
     {
         const u32 b = threadIdx.x;  // (256 threads: one table entry each) "ACGT"[sym], the first symbol in the lowest byte
         s_text[b] = ((0x54474341u >> (8 * (b & 3))) & 0xFFu) | (((0x54474341u >> (8 * ((b >> 2) & 3))) & 0xFFu) << 8) |
                     (((0x54474341u >> (8 * ((b >> 4) & 3))) & 0xFFu) << 16) | (((0x54474341u >> (8 * ((b >> 6) & 3))) & 0xFFu) << 24);
     }
     __syncthreads();
-    const u32 f = blockIdx.x * blockDim.x + threadIdx.x;  // candidates in level-major order
-    if (f >= nt) return;
-    u32 lo = 1, hi = nlev - 1;  // the level whose candidates include f: largest l with cbase[l] <= f among the levels that have any
-    while (lo < hi) {
-        const u32 mid = (lo + hi + 1) >> 1;
-        if ((mid < LDS_LEVELS ? s_cbase[mid] : lv[mid].cbase) <= f) lo = mid; else hi = mid - 1;
-    }
-    const u32 lvl = lo;
+    const u32 r = rank_lo + blockIdx.x * blockDim.x + threadIdx.x;  // output rank
+    if (r >= rank_hi) return;
+    const u32 p_first = path_off[r], p_end = path_off[r + 1];
+    const u32 o_first = pair_off[r], o_end = pair_off[r + 1];
+    const u32 lvl = p_end - p_first;  // (a tuple's path is its node's level)
+    const u32 k = src[r];
     const LevelDev L = lv[lvl];
-    const u32 k = f - L.cbase;
-    const u32 r = L.crank[k];
-    if (r < rank_lo || r >= rank_hi) return;  // (a launch fills one chunk of consecutive output ranks)
     const bool one = L.crec != nullptr;
     const uint4 cr = one ? L.crec[k] : make_uint4(0u, 0u, 0u, 0u);
     const u32 b = one ? k : L.cand_poff[k];
-    const u32 e = one ? k + 1 : (k + 1 < L.ncand ? L.cand_poff[k + 1] : L.npairs);
-    u32 o = pair_off[r];
-    const u32 o_first = o, p_first = path_off[r];
     u64 sumN = fv.d;
     double sl = 0;
     bool beyond = false;
-    for (u32 q = b; q < e; ++q, ++o) {
+    for (u32 q = b, o = o_first; o < o_end; ++q, ++o) {
         const u64 fq = one ? (((u64)cr.w << 32) | cr.z) : L.freqs[q];
-        ids[o] = one ? 0u : L.ids[q]; freqs[o] = fq;
+        if (ids) ids[o] = one ? 0u : L.ids[q];
+        freqs[o] = fq;
         sumN += fq;
         if (fv.ent && !beyond) {
             if (fq < TERM_TAB) sl += fv.terms[fq]; else beyond = true;
@@ -1242,12 +1234,13 @@ __global__ __launch_bounds__(256) void tuple_fill_kernel(u32 nt, u32 nlev, const
             fv.ent[r] = en;
             verdict = (fv.emax > 0 && (en < fv.emin || en > fv.emax)) ? EV_DROP : EV_KEEP;
         }
+        const u32 pb0 = fv.bounds[2 * fv.chunk], qb0 = fv.bounds[2 * fv.chunk + 1];
         fv.keep[r] = verdict;
-        fv.rel_path[r + fv.chunk] = p_first - fv.pb0;
-        fv.rel_pair[r + fv.chunk] = o_first - fv.qb0;
+        fv.rel_path[r + fv.chunk] = p_first - pb0;
+        fv.rel_pair[r + fv.chunk] = o_first - qb0;
         if (r + 1 == rank_hi) {  // the chunk's closing entries
-            fv.rel_path[r + 1 + fv.chunk] = path_off[r + 1] - fv.pb0;
-            fv.rel_pair[r + 1 + fv.chunk] = o - fv.qb0;
+            fv.rel_path[r + 1 + fv.chunk] = p_end - pb0;
+            fv.rel_pair[r + 1 + fv.chunk] = o_end - qb0;
         }
         const u64 md = __ballot(verdict == EV_DROP), mh = __ballot(verdict == EV_HOST);
         if ((md | mh) && (threadIdx.x & 63) == (u32)(__ffsll((long long)__ballot(1)) - 1)) {
@@ -1662,8 +1655,9 @@ struct HostPool {
 // to the chunk arrived with it (tuple_fill_kernel).  What is left for the host: the exact entropy of the few tuples whose frequencies lie
 // beyond the device's tables, with libm as the reference does it, and -- only when tuples were dropped -- moving the kept ones together.
 // With nothing dropped (always so with one sample: its LF-step kernel applied the verdict already, see KEEP_FREQS) the batch IS the
-// pinned arrays and no pass over the tuples runs here at all.
-static int emit_job(HostPool& pool, EmitSet& E, int c, u32 d, double emin, double emax, dsm_tuple_sink sink, void* ctx, u64* n_tuples, u64* n_pairs, double* ms) {
+// pinned arrays and no pass over the tuples runs here at all.  One sample has no id array in the set: its ids are zero_ids, grown as needed.
+static int emit_job(HostPool& pool, EmitSet& E, int c, u32 d, double emin, double emax, dsm_tuple_sink sink, void* ctx, std::vector<u32>& zero_ids,
+                    u64* n_tuples, u64* n_pairs, double* ms) {
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     const u32 t_lo = E.cb[c], t_hi = E.cb[c + 1];
@@ -1671,6 +1665,11 @@ static int emit_job(HostPool& pool, EmitSet& E, int c, u32 d, double emin, doubl
     u32* rel_path = (u32*)E.pin[0].p + t_lo + c;   // nt + 1 entries, the first one 0
     u32* rel_pair = (u32*)E.pin[1].p + t_lo + c;
     u32* ids = (u32*)E.pin[2].p + E.qb[c];
+    if (d == 1) {
+        const size_t need = (size_t)rel_pair[nt] + 1;
+        if (zero_ids.size() < need) zero_ids.resize(need + need / 4, 0u);
+        ids = zero_ids.data();
+    }
     u64* freqs = (u64*)E.pin[3].p + E.qb[c];
     char* paths = (char*)E.pin[4].p + E.pb[c];
     double* ent = (double*)E.pin[5].p + t_lo;
@@ -1927,6 +1926,7 @@ struct Emitter {
     double emin = 0, emax = 0;
     dsm_tuple_sink sink = nullptr;
     void* ctx = nullptr;
+    std::vector<u32> zero_ids;  // the ids of a single sample's batches (emit_job)
     // text mode (dsm_miner_mine_text): the chunks leave the card as the reference server's lines (textemit.h); nothing binary is copied
     dsm_text_sink text_sink = nullptr;
     TextEmit* te = nullptr;
@@ -1942,7 +1942,8 @@ struct Emitter {
         if (!te) return 1;
         const char* text = nullptr;
         size_t len = 0;
-        int rc = text_emit_chunk(te, t0, t1, (const u32*)E.dev[0].p, (const u32*)E.dev[1].p, (const u32*)E.dev[2].p, (const u64*)E.dev[3].p, (const char*)E.dev[4].p, d,
+        const u32* ids = d == 1 ? nullptr : (const u32*)E.dev[2].p;  // (one sample: no id array, every id 0)
+        int rc = text_emit_chunk(te, t0, t1, (const u32*)E.dev[0].p, (const u32*)E.dev[1].p, ids, (const u64*)E.dev[3].p, (const char*)E.dev[4].p, d,
                                  emin, emax, &text, &len, n_tuples, n_pairs);
         clock_gettime(CLOCK_MONOTONIC, &b);
         *ms_ += (b.tv_sec - a.tv_sec) * 1e3 + (b.tv_nsec - a.tv_nsec) * 1e-6;
@@ -1970,7 +1971,7 @@ struct Emitter {
                 timeline("  emitter: chunk landed");
                 if (!rc && set[k].cb[c + 1] > set[k].cb[c]) {
                     if (text_sink) rc = text_job(set[k], set[k].cb[c], set[k].cb[c + 1], &t, &pq, &m);
-                    else rc = emit_job(pool, set[k], c, d, emin, emax, sink, ctx, &t, &pq, &m);
+                    else rc = emit_job(pool, set[k], c, d, emin, emax, sink, ctx, zero_ids, &t, &pq, &m);
                 }
                 timeline("  emitter: chunk through the sink");
             }
@@ -2110,6 +2111,7 @@ class Engine {
     u32* d_totals = nullptr;
     u64* d_totals64 = nullptr;
     u32* h_totals = nullptr;  // pinned: [0..7] u32 totals, [8..8+MAX_LOCAL) record allocations, [300..] u64 totals
+    u32* h_bounds = nullptr;  // pinned: path / pair offsets of the pending set's chunk boundaries (finish_mine -> flush_pending)
     u64* h_childmax = nullptr;  // pinned: one per rank
     std::vector<void*> owned;
     size_t owned_bytes = 0;   // device bytes behind `owned` (page-rounded)
@@ -2127,6 +2129,7 @@ class Engine {
     ~Engine() {
         for (void* p : owned) (void)hipFree(p);
         if (h_totals) (void)hipHostFree(h_totals);
+        if (h_bounds) (void)hipHostFree(h_bounds);
         if (h_childmax) (void)hipHostFree(h_childmax);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
@@ -2381,6 +2384,7 @@ class Engine {
         if (int rc = dalloc(d_pub_tot, 8)) return rc;
         if (int rc = dalloc(d_pub_cmax, (size_t)(world > 0 ? world : 1))) return rc;
         DSM_HIP(hipHostMalloc((void**)&h_totals, 320 * sizeof(u32)));
+        DSM_HIP(hipHostMalloc((void**)&h_bounds, 2 * (EmitSet::MAX_CHUNKS + 1) * sizeof(u32)));
         DSM_HIP(hipHostMalloc((void**)&h_childmax, (size_t)(world > 0 ? world : 1) * sizeof(u64)));
         return 0;
     }
@@ -3233,9 +3237,8 @@ class Engine {
         u32* startbuf[2];
         EARENA_GET(startbuf[0], u32, maxn);
         EARENA_GET(startbuf[1], u32, maxn);
-        std::vector<u32*> crank(nlev, nullptr);
-        for (u32 l = 1; l < nlev; ++l)
-            if (L[l].ncand) EARENA_GET(crank[l], u32, L[l].ncand);
+        u32* src;
+        EARENA_GET(src, u32, nt);
         DSM_HIP(hipMemsetAsync(startbuf[0], 0, sizeof(u32), st));
         for (u32 l = 0; l + 1 < nlev; ++l) {
             u32* s_cur = startbuf[l & 1];
@@ -3243,17 +3246,18 @@ class Engine {
             hipLaunchKernelGGL((down_kernel<u32>), grid_npt(L[l].n), dim3(256), 0, st, L[l].n, s_cur, 0u, L[l].kids(), L[l + 1].sub, s_next);
             if (L[l + 1].ncand)
                 hipLaunchKernelGGL(cand_rank_kernel, grid_for(L[l + 1].ncand), dim3(256), 0, st, L[l + 1].ncand, L[l + 1].cand_node, L[l + 1].cand_poff,
-                                   L[l + 1].npairs, s_next, L[l + 1].sub, l + 1, crank[l + 1], plen, npair, L[l + 1].crec);
+                                   L[l + 1].npairs, s_next, L[l + 1].sub, l + 1, src, plen, npair, L[l + 1].crec);
         }
-        // tuple sizes -> offsets
+        // tuple sizes -> offsets; their totals the host knows already: a tuple's path is as long as its level, and a level's candidates
+        // hold its pairs (a record holds one)
         std::vector<LevelDev> lv(nlev);
-        u32 cb = 0;
+        u64 path_bytes = 0, npairs = 0;
         for (u32 l = 0; l < nlev; ++l) {
-            lv[l].pw = L[l].pw; lv[l].cand_node = L[l].cand_node; lv[l].cand_poff = L[l].cand_poff; lv[l].crec = L[l].crec; lv[l].crank = crank[l];
-            lv[l].ids = L[l].ids; lv[l].freqs = L[l].freqs; lv[l].ncand = l ? L[l].ncand : 0; lv[l].npairs = L[l].npairs;
-            lv[l].cbase = cb;
-            cb += lv[l].ncand;
+            lv[l].pw = L[l].pw; lv[l].cand_node = L[l].cand_node; lv[l].cand_poff = L[l].cand_poff; lv[l].crec = L[l].crec;
+            lv[l].ids = L[l].ids; lv[l].freqs = L[l].freqs;
+            if (l && L[l].ncand) { path_bytes += (u64)l * L[l].ncand; npairs += L[l].crec ? L[l].ncand : L[l].npairs; }
         }
+        if (path_bytes > 0xFFFFFFFFull || npairs > 0xFFFFFFFFull) return fail(DSM_E_CAPACITY, "more than 2^32 path bytes or pairs in one prefix: use a longer prefix");
         LevelDev* d_lv;
         EARENA_GET(d_lv, LevelDev, nlev);
         DSM_HIP(hipMemcpyAsync(d_lv, lv.data(), nlev * sizeof(LevelDev), hipMemcpyHostToDevice, st));
@@ -3273,21 +3277,26 @@ class Engine {
         exclusive_scan<u32, u32>(npair, pair_off, nt, stmp, d_totals + 1, st);
         DSM_HIP(hipMemcpyAsync(path_off + nt, d_totals, sizeof(u32), hipMemcpyDeviceToDevice, st));
         DSM_HIP(hipMemcpyAsync(pair_off + nt, d_totals + 1, sizeof(u32), hipMemcpyDeviceToDevice, st));
-        // chunk boundaries: consecutive tuple ranges of at least a million tuples
+        // chunk boundaries: consecutive tuple ranges of at least a million tuples (DSM_EMIT_CHUNK_TUPLES: another unit, a test hook)
+        static const u64 chunk_unit = [] {
+            const char* e = getenv("DSM_EMIT_CHUNK_TUPLES");
+            const long long n = e ? atoll(e) : 0;
+            return n > 0 ? (u64)n : (u64)(1u << 20);
+        }();
         ChunkBounds cbs;
-        cbs.n = nt >= (4u << 20) ? 4 : (nt >= (2u << 20) ? 2 : 1);
+        cbs.n = nt >= 4 * chunk_unit ? 4 : (nt >= 2 * chunk_unit ? 2 : 1);
         for (int c = 0; c <= cbs.n; ++c) cbs.tb[c] = (u32)((u64)nt * c / cbs.n);
         u32* d_bounds;
         EARENA_GET(d_bounds, u32, 2 * (EmitSet::MAX_CHUNKS + 1));
         hipLaunchKernelGGL(chunk_bounds_kernel, dim3(1), dim3(64), 0, st, cbs, path_off, pair_off, d_bounds);  // after the two sentinel copies
-        DSM_HIP(hipMemcpyAsync(h_totals + 16, d_bounds, 2 * (cbs.n + 1) * sizeof(u32), hipMemcpyDeviceToHost, st));
-        DSM_HIP(hipMemcpyAsync(h_totals, d_totals, 2 * sizeof(u32), hipMemcpyDeviceToHost, st));
-        DSM_HIP(hipStreamSynchronize(st));
-        const u64 path_bytes = h_totals[0], npairs = h_totals[1];
-        if (int rc = E.dev[2].ensure((size_t)npairs * 4)) return rc;
+        // the host needs the boundaries only in flush_pending, after read_back's synchronisation; nothing else writes h_bounds meanwhile
+        DSM_HIP(hipMemcpyAsync(h_bounds, d_bounds, 2 * (cbs.n + 1) * sizeof(u32), hipMemcpyDeviceToHost, st));
+        // one sample: every id is 0 -- no id array on the card or the bus (the emitter hands the sink zeros of its own)
+        const bool no_ids = d == 1;
+        if (!no_ids) { if (int rc = E.dev[2].ensure((size_t)npairs * 4)) return rc; }
         if (int rc = E.dev[3].ensure((size_t)npairs * 8)) return rc;
         if (int rc = E.dev[4].ensure((size_t)path_bytes)) return rc;
-        u32* d_ids = (u32*)E.dev[2].p;
+        u32* d_ids = no_ids ? nullptr : (u32*)E.dev[2].p;
         u64* d_freqs = (u64*)E.dev[3].p;
         char* d_paths = (char*)E.dev[4].p;
         emitter.text_sink = text_sink_;
@@ -3298,7 +3307,7 @@ class Engine {
             const size_t nrel = (size_t)nt + EmitSet::MAX_CHUNKS + 1;
             if (int rc = E.pin[0].ensure(nrel * 4)) return rc;
             if (int rc = E.pin[1].ensure(nrel * 4)) return rc;
-            if (int rc = E.pin[2].ensure((size_t)npairs * 4)) return rc;
+            if (!no_ids) { if (int rc = E.pin[2].ensure((size_t)npairs * 4)) return rc; }
             if (int rc = E.pin[3].ensure((size_t)npairs * 8)) return rc;
             if (int rc = E.pin[4].ensure((size_t)path_bytes)) return rc;
             if (int rc = E.pin[5].ensure((size_t)nt * 8)) return rc;
@@ -3317,12 +3326,11 @@ class Engine {
             }
             DSM_HIP(hipMemsetAsync(E.dev[9].p, 0, 2 * EmitSet::MAX_CHUNKS * sizeof(u32), st));
             fv.ent = (double*)E.dev[5].p; fv.keep = (u8*)E.dev[6].p; fv.rel_path = (u32*)E.dev[7].p; fv.rel_pair = (u32*)E.dev[8].p;
-            fv.terms = d_terms; fv.logn = d_logn; fv.d = d; fv.emin = prm.emin; fv.emax = prm.emax;
+            fv.terms = d_terms; fv.logn = d_logn; fv.d = d; fv.emin = prm.emin; fv.emax = prm.emax; fv.bounds = d_bounds;
         }
         E.nchunk = cbs.n;
-        // One fill per chunk of output ranks (its threads follow the levels, not the output order: every launch looks at all candidates and
-        // keeps the ones of its chunk), so that a chunk is on its way to the host while the next one is being filled -- what shows at
-        // the end of a pass, where nothing else hides the last prefix's copy (1 GB, 20 ms, behind a 14 ms fill).
+        // One fill per chunk of output ranks (a thread per tuple of the chunk), so that a chunk is on its way to the host while the next
+        // one is being filled -- what shows at the end of a pass, where nothing else hides the last prefix's copy.
         if (!copy_stream) DSM_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
         // The fills go out now.  The copies to the host -- blit kernels that spread over the compute units and stay for the length of a PCIe
         // transfer -- and the emitter's work are HELD BACK until the next prefix is a few levels deep (flush_pending): the first levels of
@@ -3330,18 +3338,17 @@ class Engine {
         // waited for a compute unit (measured: 300-1500 us for a one-workgroup LF-step launch that takes 10 us alone; 9 ms per pass).
         for (int c = 0; c < cbs.n; ++c) {
             const u32 t0 = cbs.tb[c], t1 = cbs.tb[c + 1];
-            fv.chunk = (u32)c; fv.pb0 = h_totals[16 + 2 * c]; fv.qb0 = h_totals[17 + 2 * c];
+            fv.chunk = (u32)c;
             fv.counts = text_mode ? nullptr : (u32*)E.dev[9].p + 2 * c;
-            hipLaunchKernelGGL(tuple_fill_kernel, grid_for(nt), dim3(256), 0, st, nt, nlev, d_lv, path_off, pair_off, d_paths, d_ids, d_freqs, t0, t1, fv);
+            if (t1 > t0)
+                hipLaunchKernelGGL(tuple_fill_kernel, grid_for(t1 - t0), dim3(256), 0, st, nlev, d_lv, path_off, pair_off, src, d_paths, d_ids, d_freqs, t0, t1, fv);
             DSM_HIP(hipGetLastError());
             E.cb[c] = t0; E.cb[c + 1] = t1;
             if (!E.cready[c]) DSM_HIP(hipEventCreateWithFlags(&E.cready[c], hipEventDisableTiming));
             if (!chunk_filled[c]) DSM_HIP(hipEventCreateWithFlags(&chunk_filled[c], hipEventDisableTiming));
             DSM_HIP(hipEventRecord(chunk_filled[c], st));
-            pend.off[2 * c] = h_totals[16 + 2 * c]; pend.off[2 * c + 1] = h_totals[17 + 2 * c];
         }
-        pend.off[2 * cbs.n] = h_totals[16 + 2 * cbs.n]; pend.off[2 * cbs.n + 1] = h_totals[17 + 2 * cbs.n];
-        pend.E = &E; pend.nchunk = cbs.n; pend.text = text_mode;
+        pend.E = &E; pend.nchunk = cbs.n; pend.text = text_mode; pend.ids = !no_ids;
         E.nt = nt;
         emitter.d = d; emitter.emin = prm.emin; emitter.emax = prm.emax; emitter.sink = sink; emitter.ctx = ctx;
         *ready = true;
@@ -3351,8 +3358,7 @@ class Engine {
     struct PendingEmit {
         EmitSet* E = nullptr;
         int nchunk = 0;
-        bool text = false, submit = false;
-        u64 off[2 * (EmitSet::MAX_CHUNKS + 1)];  // path / pair offsets of the chunk boundaries
+        bool text = false, submit = false, ids = true;
     } pend;
     int flush_pending() {
         if (!pend.E || !pend.submit) return 0;
@@ -3371,7 +3377,8 @@ class Engine {
                 continue;
             }
             DSM_HIP(hipStreamWaitEvent(copy_stream, chunk_filled[c], 0));
-            const u64 pb0 = pend.off[2 * c], qb0 = pend.off[2 * c + 1], pb1 = pend.off[2 * (c + 1)], qb1 = pend.off[2 * (c + 1) + 1];
+            // (the path / pair offsets of the chunk boundaries: copied by finish_mine, landed by read_back's synchronisation)
+            const u64 pb0 = h_bounds[2 * c], qb0 = h_bounds[2 * c + 1], pb1 = h_bounds[2 * (c + 1)], qb1 = h_bounds[2 * (c + 1) + 1];
             // offsets relative to the chunk (its own closing entry included), entropies, verdicts, the chunk's counts
             DSM_HIP(hipMemcpyAsync((u32*)E.pin[0].p + t0 + c, (const u32*)E.dev[7].p + t0 + c, ((size_t)(t1 - t0) + 1) * 4, hipMemcpyDeviceToHost, copy_stream));
             DSM_HIP(hipMemcpyAsync((u32*)E.pin[1].p + t0 + c, (const u32*)E.dev[8].p + t0 + c, ((size_t)(t1 - t0) + 1) * 4, hipMemcpyDeviceToHost, copy_stream));
@@ -3382,7 +3389,7 @@ class Engine {
             DSM_HIP(hipMemcpyAsync((u32*)E.pin[9].p + 2 * c, (const u32*)E.dev[9].p + 2 * c, 2 * sizeof(u32), hipMemcpyDeviceToHost, copy_stream));
             E.pb[c] = pb0; E.qb[c] = qb0;
             if (qb1 > qb0) {
-                DSM_HIP(hipMemcpyAsync((u32*)E.pin[2].p + qb0, d_ids + qb0, (qb1 - qb0) * 4, hipMemcpyDeviceToHost, copy_stream));
+                if (pend.ids) DSM_HIP(hipMemcpyAsync((u32*)E.pin[2].p + qb0, d_ids + qb0, (qb1 - qb0) * 4, hipMemcpyDeviceToHost, copy_stream));
                 DSM_HIP(hipMemcpyAsync((u64*)E.pin[3].p + qb0, d_freqs + qb0, (qb1 - qb0) * 8, hipMemcpyDeviceToHost, copy_stream));
             }
             if (pb1 > pb0) DSM_HIP(hipMemcpyAsync((char*)E.pin[4].p + pb0, d_paths + pb0, pb1 - pb0, hipMemcpyDeviceToHost, copy_stream));

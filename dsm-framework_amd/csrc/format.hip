@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void te_len_kernel(u32 t0, u32 t1, const u32* 
     const u64 v = fixed6_of(ent[r - t0], &neg, &ok);
     if (!ok) { atomicOr(bad, 1u); len[r - t0] = 0; return; }  // (an entropy is at most log2(273): cannot happen)
     u32 n = (path_off[r + 1] - path_off[r]) + 1u + (neg ? 1u : 0u) + dec_digits(v / 1000000ull) + 7u;
-    for (u32 q = pair_off[r]; q < pair_off[r + 1]; ++q) n += 2u + dec_digits(ids[q]) + dec_digits(freqs[q]);
+    for (u32 q = pair_off[r]; q < pair_off[r + 1]; ++q) n += 2u + dec_digits(ids ? ids[q] : 0u) + dec_digits(freqs[q]);
     len[r - t0] = n + 1u;
     atomicAdd(counts, 1ull);
     atomicAdd(counts + 1, (unsigned long long)(pair_off[r + 1] - pair_off[r]));
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void te_write_kernel(u32 t0, u32 t1, const u32
     p += 6;
     for (u32 q = pair_off[r]; q < pair_off[r + 1]; ++q) {
         *p++ = ' ';
-        const u64 id = ids[q], f = freqs[q];
+        const u64 id = ids ? ids[q] : 0u, f = freqs[q];
         p += put_dec(p, id, dec_digits(id));
         *p++ = ':';
         p += put_dec(p, f, dec_digits(f));
