@@ -4,6 +4,7 @@
     python bench.py --gpus N --steps K --warmup W
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py ... --dump-outputs DIR     (also writes what the last timed step computed, DIR/<name>.npy)
+    python bench.py ... --full                 (and everything beyond the headline; minutes)
 
 Workload (BASELINE.json configs[1] at N=1, configs[2] at N>1): one synthetic read set per GPU,
 10^7 reads x 100 bp from a shared 50 Mbp random genome (20x, 0.5 % substitutions; seeds 42+rank), indexed as
@@ -14,6 +15,12 @@ Index construction and loading are outside the timed region; inputs are HBM resi
 
 One JSON line on rank 0; `value` = emitted trie nodes ('(' tokens, EnumerateQuery.cpp:209) summed over all
 samples and steps / max-over-ranks wall time.
+
+A plain run sets up, warms up, times the steps, writes its outputs when asked and prints the line; `roofline` and `detail`
+come from the counters of the timed steps.  Whatever takes runs of its own waits for --full (default N=1 configuration only):
+the text passes, the CPU baselines (the unmodified reference client and our port) and the extra records (64-bit positions,
+wire streams, the server side, 8 and 64 samples on one GPU, 4-Gbase samples).  Indexes are built in a directory of the run's
+own, removed at exit, unless --workdir / DSM_BENCH_DIR names one to keep them in (files found there are reused).
 """
 import argparse
 import ctypes
@@ -43,13 +50,15 @@ def parse():
     ap.add_argument("--prefix-len", type=int, default=-1, help="k-mer prefix length of the chunks; default 1")
     ap.add_argument("--fmin", type=int, default=10)
     ap.add_argument("--emax", type=float, default=2.0)
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline leg (rank 0, N=1)")
+    ap.add_argument("--full", action="store_true", help="after the line's own steps, also the measurements that take runs of their own "
+                    "(default N=1 configuration): text passes, CPU baselines, extra records; minutes")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline leg (--full; rank 0, N=1)")
     ap.add_argument("--force-exchange", action="store_true", help="rehearsal at N=1: drive the whole multi-rank exchange path (send buffer, "
                     "one RCCL all-gather per level through torch.distributed, lanes, status words) with a world of one")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra records of the default N=1 run (64-bit positions; eight samples on one GPU)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without any of its passes: neither text passes, CPU baselines nor extra records")
+    ap.add_argument("--no-extras", action="store_true", help="--full without its extra records (64-bit positions; eight samples on one GPU)")
     ap.add_argument("--extras", default=os.environ.get("DSM_BENCH_EXTRAS", "all"),
-                    help="which extra records: all, or a comma list of u64,stream,server,d8,d64,big (big = configs[3]: 4-Gbase samples)")
+                    help="which extra records --full adds: all, or a comma list of u64,stream,server,d8,d64,big (big = configs[3]: 4-Gbase samples)")
     ap.add_argument("--pmin", type=int, default=-1, help="metaserver -P; default 1 for a single sample, else 2")
     ap.add_argument("--pmax", type=int, default=0, help="metaserver --pmax (BASELINE configs[3]: 8, configs[4]: 1)")
     ap.add_argument("--wide", action="store_true", help="force 64-bit positions (the code path of n > 2^32, BASELINE configs[3])")
@@ -62,7 +71,9 @@ def parse():
                          "partition, prefix k is merged by rank k %% N alone (columns gathered to it, the union's child masks broadcast "
                          "back), one lane per owner so that every rank is the server of one lane and a client in the others; 'both' = one "
                          "after the other on the same indexes, both values in the line, the faster one as the headline")
-    ap.add_argument("--workdir", default=os.environ.get("DSM_BENCH_DIR", "/tmp/dsm_bench"))
+    ap.add_argument("--workdir", default=os.environ.get("DSM_BENCH_DIR"),
+                    help="directory that keeps the indexes between runs (files found there are reused); default: a directory of the "
+                         "run's own, removed at exit")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step delivered to its caller as DIR/<name>.npy (float32/float64, "
                          "at most 64 MB in all: exact totals and a seeded sample of the tuples; see write_dump).  The capture runs inside "
@@ -326,7 +337,7 @@ def extra_records(args, dev, local, pydsm, ix, path, prefixes, pmin):
         nbig = int(os.environ.get("DSM_BENCH_BIG_SAMPLES", "8"))
         bpaths = []
         t0 = time.time()
-        for k in range(nbig):  # (the files tests/test_fullsize_gpu.py::test_real_bwt_beyond_2_32 builds: shared when both run on one box)
+        for k in range(nbig):  # (the files tests/test_fullsize_gpu.py::test_real_bwt_beyond_2_32 builds: shared through DSM_BENCH_DIR)
             pth = os.path.join(args.workdir, "real-%d%s.fmi" % (big, "" if k == 0 else ("-b" if k == 1 else "-%d" % k)))
             if not os.path.exists(pth):
                 codes = builder.synth_reads(4242 + k, big, args.rlen, 5 * big, args.sub_rate, device=dev, private_frac=0.05 if k else 0.0)
@@ -618,6 +629,12 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         raise SystemExit(subprocess.call(cmd))
+    if args.workdir is None:  # nothing from an earlier run: the indexes are built afresh, in a directory of this run's own
+        import atexit
+        import shutil
+        import tempfile
+        args.workdir = tempfile.mkdtemp(prefix="dsm_bench.")
+        atexit.register(shutil.rmtree, args.workdir, True)
     import torch
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -875,13 +892,13 @@ def main():
     if args.dump_outputs is not None:
         nb = write_dump(args.dump_outputs, lanes, len(prefixes), world, rank)
         print("bench: rank %d wrote %.1f MB of outputs to %s" % (rank, nb / 1e6, args.dump_outputs), file=sys.stderr, flush=True)
-    # Text (metaserver.cpp:472-484's printf loop) is outside the timed region of `value` (the sink receives binary batches).  One more
+    # Text (metaserver.cpp:472-484's printf loop) is outside the timed region of `value` (the sink receives binary batches).  --full: one more
     # pass with a sink that formats every batch on the GPU (dsm_formatter_format, the drop-in's way since round 4), timed twice: the
     # calls alone (`format_ms_per_step`) and the whole pass (`text_pass_ms`: what a user of the text surface waits for; the formatter's
     # transfers share the bus with the next prefix's tuples).  `format_host_ms_per_step`: the same text from the host's snprintf loop,
     # on a tenth of the batches, scaled -- the round-3 path, kept as the checker.
     format_ms, format_bytes, text_pass_ms, format_host_ms, text_pass_formatter_ms, text_mode_bytes = None, 0, None, None, None, None
-    if rank == 0 and world == 1 and not args.stream_mode and not forced and not args.no_cpu:  # (--no-cpu: profiling runs, exactly steps + warmup passes)
+    if args.full and not args.no_cpu and rank == 0 and world == 1 and not args.stream_mode and not forced:
         import ctypes as C
         acc = {"s": 0.0, "bytes": 0, "host_s": 0.0, "host_bytes": 0, "k": 0}
         fm = pydsm.Formatter(local)
@@ -1025,8 +1042,9 @@ def main():
         if both is not None:
             out["exchange_modes"] = both
         print("bench: gpu leg done: %.3e substrings/s, %.1f ms/step" % (out["value"], out["ms_per_step"]), file=sys.stderr, flush=True)
+        # --full: what takes runs of its own, next to the line's steps (the default N=1 configuration only)
         default_cfg = world == 1 and args.nlocal == 1 and not args.stream_mode and not forced
-        if default_cfg and not args.no_cpu:
+        if default_cfg and args.full and not args.no_cpu:
             ref = None
             try:
                 ref = cpu_baseline_reference(path, args, ix, pydsm)
@@ -1038,7 +1056,7 @@ def main():
                 out["cpu_baseline"] = ref
             else:
                 out["cpu_baseline"] = port
-        if default_cfg and not args.no_extras and not args.no_cpu and not args.wide and args.reads >= 1_000_000:
+        if default_cfg and args.full and not args.no_extras and not args.no_cpu and not args.wide and args.reads >= 1_000_000:
             out["extra_records"] = extra_records(args, dev, local, pydsm, ix, path, prefixes, pmin)
         print(json.dumps(out), flush=True)
     for x in ixs:
