@@ -1133,20 +1133,25 @@ __global__ __launch_bounds__(256) void down_kernel(u32 F, const T* __restrict__ 
     }
 }
 
-// candidate k of a level gets its post-order rank among all candidates of the prefix; the tuple's sizes and where it came from (its
-// index in the level: the level itself is its path length) go to their place in output order (the ranks of neighbouring candidates are
-// far apart: the levels are in colex order, the output in trie order)
+// What a candidate leaves at its rank r: its index k in its level and its level (= its path length) side by side, one scattered 8-byte
+// store (the ranks of neighbouring candidates are far apart: the levels are in colex order, the output in trie order).  The scan of the
+// path offsets reads the level through the conversion.
+struct RankSlot {
+    u32 k, level;
+    __device__ explicit operator u32() const { return level; }
+};
+// candidate k of a level gets its post-order rank among all candidates of the prefix; its slot and, unless every tuple has one pair
+// (npair null), its pair count go to their place in output order
 // (crec: the records the advance sweep of a single sample stored -- node, 0, frequency -- instead of the four arrays: one pair each)
 __global__ void cand_rank_kernel(u32 ncand, const u32* __restrict__ cand_node, const u32* __restrict__ cand_poff, u32 npairs,
-                                 const u32* __restrict__ start, const u32* __restrict__ sub, u32 level, u32* __restrict__ src,
-                                 u32* __restrict__ plen, u32* __restrict__ npair, const uint4* __restrict__ crec) {
+                                 const u32* __restrict__ start, const u32* __restrict__ sub, u32 level, RankSlot* __restrict__ slot,
+                                 u32* __restrict__ npair, const uint4* __restrict__ crec) {
     u32 k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= ncand) return;
     u32 v = crec ? crec[k].x : cand_node[k];
     u32 r = start[v] + sub[v] - 1;
-    src[r] = k;
-    plen[r] = level;
-    npair[r] = crec ? 1u : (k + 1 < ncand ? cand_poff[k + 1] : npairs) - cand_poff[k];
+    slot[r] = RankSlot{k, level};
+    if (npair) npair[r] = crec ? 1u : (k + 1 < ncand ? cand_poff[k + 1] : npairs) - cand_poff[k];
 }
 
 struct LevelDev {
@@ -1159,15 +1164,16 @@ struct LevelDev {
 };
 
 // offsets of the chunk boundaries (path bytes, pairs): out[2c], out[2c+1] for boundary tuple tb[c] (read by the fills and, copied, by the host)
+// (pair_off null: one pair per tuple, the pair offset of a tuple is its rank -- also in the fills)
 constexpr int EMIT_MAX_CHUNKS = 8;
 struct ChunkBounds { u32 tb[EMIT_MAX_CHUNKS + 1]; int n; };
 __global__ void chunk_bounds_kernel(ChunkBounds cbs, const u32* __restrict__ path_off, const u32* __restrict__ pair_off, u32* __restrict__ out) {
     const int c = threadIdx.x;
-    if (c <= cbs.n) { out[2 * c] = path_off[cbs.tb[c]]; out[2 * c + 1] = pair_off[cbs.tb[c]]; }
+    if (c <= cbs.n) { out[2 * c] = path_off[cbs.tb[c]]; out[2 * c + 1] = pair_off ? pair_off[cbs.tb[c]] : cbs.tb[c]; }
 }
 
 // Paths and pairs of the tuples of one chunk of output ranks.  Thread r fills the tuple of rank r: its level is its path length, its
-// candidate index in that level src[r] (cand_rank_kernel), so neighbouring lanes write neighbouring path bytes, pairs and verdicts.
+// candidate index in that level slot[r].k (cand_rank_kernel), so neighbouring lanes write neighbouring path bytes, pairs and verdicts.
 // A path is put together from the path words of the node and of its ancestors at the chunk boundaries (levels 16, 32, ...): 16 symbols
 // per dependent load.
 // What the host emitter used to compute per tuple (emit_job's first pass, 3.4 ms of sixteen threads per chunk of four million tuples,
@@ -1190,7 +1196,7 @@ struct FillVerdict {
 };
 // ids null: no id array (one sample, every id 0)
 __global__ __launch_bounds__(256) void tuple_fill_kernel(u32 nlev, const LevelDev* __restrict__ lv, const u32* __restrict__ path_off,
-                                                         const u32* __restrict__ pair_off, const u32* __restrict__ src, char* __restrict__ paths,
+                                                         const u32* __restrict__ pair_off, const RankSlot* __restrict__ slot, char* __restrict__ paths,
                                                          u32* __restrict__ ids, u64* __restrict__ freqs, u32 rank_lo, u32 rank_hi, FillVerdict fv) {
     // the levels' path-word arrays are read by every walk: kept in LDS, with the text of every byte of four symbols
     constexpr u32 LDS_LEVELS = 1024;
@@ -1207,9 +1213,9 @@ __global__ __launch_bounds__(256) void tuple_fill_kernel(u32 nlev, const LevelDe
     const u32 r = rank_lo + blockIdx.x * blockDim.x + threadIdx.x;  // output rank
     if (r >= rank_hi) return;
     const u32 p_first = path_off[r], p_end = path_off[r + 1];
-    const u32 o_first = pair_off[r], o_end = pair_off[r + 1];
+    const u32 o_first = pair_off ? pair_off[r] : r, o_end = pair_off ? pair_off[r + 1] : r + 1;
     const u32 lvl = p_end - p_first;  // (a tuple's path is its node's level)
-    const u32 k = src[r];
+    const u32 k = slot[r].k;
     const LevelDev L = lv[lvl];
     const bool one = L.crec != nullptr;
     const uint4 cr = one ? L.crec[k] : make_uint4(0u, 0u, 0u, 0u);
@@ -3228,17 +3234,19 @@ class Engine {
             // (a level outside the emitted depth range has no candidates of its own: no word array)
             hipLaunchKernelGGL((up_bits_kernel<u32>), grid_npt(L[l].n), dim3(256), 0, st, L[l].n, L[l].cand_bits, L[l].kids(), child_sub, L[l].sub);
         }
-        // top-down: start offsets (two rolling arrays); every candidate's post-order rank, and its sizes at that rank
-        u32 *plen, *npair;
-        EARENA_GET(plen, u32, nt);
-        EARENA_GET(npair, u32, nt);
+        const bool text_mode = text_sink_ != nullptr;  // the emitter formats the chunks on the card: no binary copies, no pinned arrays
+        // one sample, binary batches: every tuple has one pair, the pair offset of rank r is r -- no pair counts, no scan of them
+        const bool one_pair = d == 1 && !text_mode;
+        // top-down: start offsets (two rolling arrays); every candidate's post-order rank, and its slot and sizes at that rank
+        u32* npair = nullptr;
+        if (!one_pair) EARENA_GET(npair, u32, nt);
         u32 maxn = 1;
         for (u32 l = 0; l < nlev; ++l) maxn = L[l].n > maxn ? L[l].n : maxn;
         u32* startbuf[2];
         EARENA_GET(startbuf[0], u32, maxn);
         EARENA_GET(startbuf[1], u32, maxn);
-        u32* src;
-        EARENA_GET(src, u32, nt);
+        RankSlot* slot;
+        EARENA_GET(slot, RankSlot, nt);
         DSM_HIP(hipMemsetAsync(startbuf[0], 0, sizeof(u32), st));
         for (u32 l = 0; l + 1 < nlev; ++l) {
             u32* s_cur = startbuf[l & 1];
@@ -3246,7 +3254,7 @@ class Engine {
             hipLaunchKernelGGL((down_kernel<u32>), grid_npt(L[l].n), dim3(256), 0, st, L[l].n, s_cur, 0u, L[l].kids(), L[l + 1].sub, s_next);
             if (L[l + 1].ncand)
                 hipLaunchKernelGGL(cand_rank_kernel, grid_for(L[l + 1].ncand), dim3(256), 0, st, L[l + 1].ncand, L[l + 1].cand_node, L[l + 1].cand_poff,
-                                   L[l + 1].npairs, s_next, L[l + 1].sub, l + 1, src, plen, npair, L[l + 1].crec);
+                                   L[l + 1].npairs, s_next, L[l + 1].sub, l + 1, slot, npair, L[l + 1].crec);
         }
         // tuple sizes -> offsets; their totals the host knows already: a tuple's path is as long as its level, and a level's candidates
         // hold its pairs (a record holds one)
@@ -3268,15 +3276,15 @@ class Engine {
         if (!E.ready) DSM_HIP(hipEventCreateWithFlags(&E.ready, hipEventDisableTiming));
         if (!copy_stream) DSM_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
         if (int rc = E.dev[0].ensure(((size_t)nt + 1) * 4)) return rc;
-        if (int rc = E.dev[1].ensure(((size_t)nt + 1) * 4)) return rc;
+        if (!one_pair) { if (int rc = E.dev[1].ensure(((size_t)nt + 1) * 4)) return rc; }
         u32* path_off = (u32*)E.dev[0].p;
-        u32* pair_off = (u32*)E.dev[1].p;
+        u32* pair_off = one_pair ? nullptr : (u32*)E.dev[1].p;
         u32* stmp;
         EARENA_GET(stmp, u32, scan_tmp_elems(nt) + 8);
-        exclusive_scan<u32, u32>(plen, path_off, nt, stmp, d_totals, st);
-        exclusive_scan<u32, u32>(npair, pair_off, nt, stmp, d_totals + 1, st);
+        exclusive_scan<RankSlot, u32>(slot, path_off, nt, stmp, d_totals, st);
+        if (!one_pair) exclusive_scan<u32, u32>(npair, pair_off, nt, stmp, d_totals + 1, st);
         DSM_HIP(hipMemcpyAsync(path_off + nt, d_totals, sizeof(u32), hipMemcpyDeviceToDevice, st));
-        DSM_HIP(hipMemcpyAsync(pair_off + nt, d_totals + 1, sizeof(u32), hipMemcpyDeviceToDevice, st));
+        if (!one_pair) DSM_HIP(hipMemcpyAsync(pair_off + nt, d_totals + 1, sizeof(u32), hipMemcpyDeviceToDevice, st));
         // chunk boundaries: consecutive tuple ranges of at least a million tuples (DSM_EMIT_CHUNK_TUPLES: another unit, a test hook)
         static const u64 chunk_unit = [] {
             const char* e = getenv("DSM_EMIT_CHUNK_TUPLES");
@@ -3300,7 +3308,6 @@ class Engine {
         u64* d_freqs = (u64*)E.dev[3].p;
         char* d_paths = (char*)E.dev[4].p;
         emitter.text_sink = text_sink_;
-        const bool text_mode = text_sink_ != nullptr;  // the emitter formats the chunks on the card: no binary copies, no pinned arrays
         FillVerdict fv;
         memset(&fv, 0, sizeof fv);
         if (!text_mode) {
@@ -3341,7 +3348,7 @@ class Engine {
             fv.chunk = (u32)c;
             fv.counts = text_mode ? nullptr : (u32*)E.dev[9].p + 2 * c;
             if (t1 > t0)
-                hipLaunchKernelGGL(tuple_fill_kernel, grid_for(t1 - t0), dim3(256), 0, st, nlev, d_lv, path_off, pair_off, src, d_paths, d_ids, d_freqs, t0, t1, fv);
+                hipLaunchKernelGGL(tuple_fill_kernel, grid_for(t1 - t0), dim3(256), 0, st, nlev, d_lv, path_off, pair_off, slot, d_paths, d_ids, d_freqs, t0, t1, fv);
             DSM_HIP(hipGetLastError());
             E.cb[c] = t0; E.cb[c + 1] = t1;
             if (!E.cready[c]) DSM_HIP(hipEventCreateWithFlags(&E.cready[c], hipEventDisableTiming));
