@@ -42,6 +42,7 @@
 #include "textemit.h"
 #include "engine_api.h"
 #include "emit_runs.h"
+#include "emit_fill.h"
 
 namespace dsm {
 
@@ -101,9 +102,12 @@ static inline dim3 grid_npt(u64 n) { return dim3((unsigned)((n + 256ull * NPT - 
 
 
 // DSM_TIMELINE=1: host time stamps of a mining call on stderr (milliseconds since the first stamp), a debugging aid
-static inline void timeline(const char* what, const char* arg = "") {
+static inline bool timeline_on() {
     static const bool on = getenv("DSM_TIMELINE") != nullptr;
-    if (!on) return;
+    return on;
+}
+static inline void timeline(const char* what, const char* arg = "") {
+    if (!timeline_on()) return;
     static const auto t0 = std::chrono::steady_clock::now();
     fprintf(stderr, "dsm timeline %9.3f ms  %s %s\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), what, arg);
 }
@@ -1181,12 +1185,16 @@ __global__ void chunk_bounds_kernel(ChunkBounds cbs, const u32* __restrict__ pat
 // same order, one division, one subtraction -- IEEE double, bit-identical to the host's), the emin / emax verdict (:413) and the offsets
 // relative to the chunk (a batch's offsets start at 0).  The thread that fills a tuple has its frequencies in registers.  A frequency or
 // a total beyond the tables (a few hundred nodes at the top of a pass) leaves the tuple to the host (EV_HOST).
+// One sample's binary batches (every tuple has one pair) keep the verdict and the counts, computed in registers, and leave three arrays
+// off the card and the bus: the pair offsets (0, 1, 2, ... in every chunk), the entropy (the host derives it from the frequency, bit for
+// bit: emit_fill.h) and, with 32-bit positions, the upper half of the frequency -- 16 of a tuple's 46.5 bytes at the benchmark's size.
 constexpr u8 EV_DROP = 0, EV_KEEP = 1, EV_HOST = 2;
 struct FillVerdict {
-    double* ent;          // per tuple (output rank); null: no verdicts (text mode computes its own)
-    u8* keep;
+    u8* keep;             // per tuple (output rank); null: no verdicts (text mode computes its own)
+    double* ent;          // null: not stored -- one pair per tuple, the host derives it from the frequency (emit_fill.h)
     u32* rel_path;        // offsets relative to the chunk, chunk c at [rank_lo + c, rank_hi + c]
-    u32* rel_pair;
+    u32* rel_pair;        // null: not stored -- one pair per tuple, every chunk's array is 0, 1, 2, ...
+    u32* freq32;          // one pair per tuple and 32-bit positions: the frequency of rank r as four bytes, instead of freqs
     u32* counts;          // of the chunk: [0] dropped, [1] left to the host
     const double* terms;  // device copies of term_table() / logn_table()
     const double* logn;
@@ -1226,27 +1234,27 @@ __global__ __launch_bounds__(256) void tuple_fill_kernel(u32 nlev, const LevelDe
     for (u32 q = b, o = o_first; o < o_end; ++q, ++o) {
         const u64 fq = one ? (((u64)cr.w << 32) | cr.z) : L.freqs[q];
         if (ids) ids[o] = one ? 0u : L.ids[q];
-        freqs[o] = fq;
+        if (fv.freq32) fv.freq32[o] = (u32)fq; else freqs[o] = fq;
         sumN += fq;
-        if (fv.ent && !beyond) {
+        if (fv.keep && !beyond) {
             if (fq < TERM_TAB) sl += fv.terms[fq]; else beyond = true;
         }
     }
-    if (fv.ent) {
+    if (fv.keep) {
         beyond = beyond || sumN >= LOGN_TAB;
         u8 verdict = EV_HOST;
         if (!beyond) {
             const double en = fv.logn[sumN] - sl / (double)sumN;
-            fv.ent[r] = en;
+            if (fv.ent) fv.ent[r] = en;
             verdict = (fv.emax > 0 && (en < fv.emin || en > fv.emax)) ? EV_DROP : EV_KEEP;
         }
         const u32 pb0 = fv.bounds[2 * fv.chunk], qb0 = fv.bounds[2 * fv.chunk + 1];
         fv.keep[r] = verdict;
         fv.rel_path[r + fv.chunk] = p_first - pb0;
-        fv.rel_pair[r + fv.chunk] = o_first - qb0;
+        if (fv.rel_pair) fv.rel_pair[r + fv.chunk] = o_first - qb0;
         if (r + 1 == rank_hi) {  // the chunk's closing entries
             fv.rel_path[r + 1 + fv.chunk] = p_end - pb0;
-            fv.rel_pair[r + 1 + fv.chunk] = o_end - qb0;
+            if (fv.rel_pair) fv.rel_pair[r + 1 + fv.chunk] = o_end - qb0;
         }
         const u64 md = __ballot(verdict == EV_DROP), mh = __ballot(verdict == EV_HOST);
         if ((md | mh) && (threadIdx.x & 63) == (u32)(__ffsll((long long)__ballot(1)) - 1)) {
@@ -1580,8 +1588,13 @@ struct DevGrow {  // device buffer that only grows
     ~DevGrow() { if (p) (void)hipFree(p); }
 };
 struct EmitSet {
-    DevGrow dev[10];  // the five arrays on the device (they outlive the arena while the copy stream drains them), then what the fill
-                      // adds for the host: [5] entropies, [6] verdicts, [7] / [8] offsets relative to the chunks, [9] per-chunk counts
+    DevGrow dev[11];  // the five arrays on the device (they outlive the arena while the copy stream drains them), then what the fill
+                      // adds for the host: [5] entropies, [6] verdicts, [7] / [8] offsets relative to the chunks, [9] per-chunk counts,
+                      // [10] four-byte frequencies (narrow)
+    // One sample, binary batches (one_pair): every tuple has one pair.  The pair offsets of any chunk are 0, 1, 2, ... and the entropy
+    // is a function of the frequency: neither is stored on the card or crosses the bus ([1], [5], [8] unused; emit_job makes them up).
+    // narrow: positions are 32-bit as well, the frequencies cross as four bytes ([10] instead of [3]) and the host widens them.
+    bool one_pair = false, narrow = false;
     hipEvent_t ready = nullptr;  // recorded on the copy stream after the last device-to-host copy
     // A large set travels in chunks of consecutive tuples: chunk c is filled, copied and handed to the sink while the
     // following ones are still on their way (the tail of a prefix is one chunk of host work, not the whole set).
@@ -1590,8 +1603,9 @@ struct EmitSet {
     u32 cb[MAX_CHUNKS + 1] = {0};            // tuple boundaries
     hipEvent_t cready[MAX_CHUNKS] = {nullptr};  // chunk c has landed in pinned memory
     int device = 0;
-    PinBuf pin[10];  // [0] / [1] offsets relative to the chunks (chunk c at [cb[c] + c, cb[c + 1] + c]), [2] ids, [3] freqs, [4] paths (device order
-                     // = post-order rank), [5] entropies, [6] verdicts, [9] per-chunk counts {dropped, left to the host}
+    PinBuf pin[11];  // [0] / [1] offsets relative to the chunks (chunk c at [cb[c] + c, cb[c + 1] + c]), [2] ids, [3] freqs, [4] paths (device order
+                     // = post-order rank), [5] entropies, [6] verdicts, [9] per-chunk counts {dropped, left to the host}, [10] four-byte
+                     // frequencies as they arrive (narrow; [3] and [5] are then written by the host, see one_pair)
     u64 pb[MAX_CHUNKS + 1] = {0}, qb[MAX_CHUNKS + 1] = {0};  // path byte / pair at which chunk c starts
     RawBuf out[6];   // o_path, o_pair, ent, paths, ids, freqs (kept tuples only)
     u32 nt = 0;
@@ -1657,19 +1671,30 @@ struct HostPool {
     }
 };
 
-// One chunk of a prefix's tuples, landed in pinned memory, to the sink.  The entropies, the emin / emax verdicts and the offsets relative
-// to the chunk arrived with it (tuple_fill_kernel).  What is left for the host: the exact entropy of the few tuples whose frequencies lie
-// beyond the device's tables, with libm as the reference does it, and -- only when tuples were dropped -- moving the kept ones together.
-// With nothing dropped (always so with one sample: its LF-step kernel applied the verdict already, see KEEP_FREQS) the batch IS the
-// pinned arrays and no pass over the tuples runs here at all.  One sample has no id array in the set: its ids are zero_ids, grown as needed.
+// One chunk of a prefix's tuples, landed in pinned memory, to the sink.  The emin / emax verdicts and the path offsets relative to the
+// chunk arrived with it (tuple_fill_kernel), and with several samples the entropies and pair offsets too.  One sample's chunk (E.one_pair)
+// brings neither: its pair offsets are the emitter's array 0, 1, 2, ... (iota), its entropies -- and from four-byte frequencies its
+// eight-byte ones -- are one pass of the pool over the chunk (emit_fill.h); its ids are zero_ids.  Both arrays grow as needed.
+// What else is left for the host: the exact entropy of the few tuples whose frequencies lie beyond the device's tables, with libm as the
+// reference does it, and -- only when tuples were dropped -- moving the kept ones together.  With nothing dropped (always so with one
+// sample: its LF-step kernel applied the verdict already, see KEEP_FREQS) the batch IS the pinned arrays.
 static int emit_job(HostPool& pool, EmitSet& E, int c, u32 d, double emin, double emax, dsm_tuple_sink sink, void* ctx, std::vector<u32>& zero_ids,
-                    u64* n_tuples, u64* n_pairs, double* ms) {
+                    std::vector<u32>& iota, u64* n_tuples, u64* n_pairs, double* ms) {
     struct timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     const u32 t_lo = E.cb[c], t_hi = E.cb[c + 1];
     const u32 nt = t_hi - t_lo;  // tuples [t_lo, t_hi) of the set
+    const bool one_pair = E.one_pair;
     u32* rel_path = (u32*)E.pin[0].p + t_lo + c;   // nt + 1 entries, the first one 0
-    u32* rel_pair = (u32*)E.pin[1].p + t_lo + c;
+    u32* rel_pair = one_pair ? nullptr : (u32*)E.pin[1].p + t_lo + c;
+    if (one_pair) {  // (shared by every chunk and run: never written after it has grown)
+        const size_t have = iota.size(), need = (size_t)nt + 1;
+        if (have < need) {
+            iota.resize(need + need / 4);
+            for (size_t q = have; q < iota.size(); ++q) iota[q] = (u32)q;
+        }
+        rel_pair = iota.data();
+    }
     u32* ids = (u32*)E.pin[2].p + E.qb[c];
     if (d == 1) {
         const size_t need = (size_t)rel_pair[nt] + 1;
@@ -1682,15 +1707,43 @@ static int emit_job(HostPool& pool, EmitSet& E, int c, u32 d, double emin, doubl
     u8* keep = (u8*)E.pin[6].p + t_lo;
     const u32* counts = (const u32*)E.pin[9].p + 2 * c;
     u64 ndrop = counts[0];
+    if (one_pair) {  // entropies (and eight-byte frequencies) of the chunk from its frequencies; E.qb[c] == t_lo
+        const u32* staged = E.narrow ? (const u32*)E.pin[10].p + t_lo : nullptr;
+        const double* terms = term_table();
+        const double* logn = logn_table();
+        unsigned nth = host_threads();
+        if (nt < 65536) nth = 1;
+        const u32 per = (nt + nth - 1) / nth;
+        auto fill = [&](unsigned t) {
+            const u32 lo = t * per < nt ? t * per : nt, hi = lo + per < nt ? lo + per : nt;
+            fill_from_freqs(staged, freqs, ent, keep, EV_HOST, terms, logn, lo, hi);
+        };
+        if (nth > 1) pool.run(nth, fill); else fill(0u);
+    }
     if (counts[1]) {  // frequencies of 65536 and more, or a total of 2^20 and more (a few nodes at the top of a pass)
-        for (u8* q = keep; (q = (u8*)memchr(q, EV_HOST, (size_t)(keep + nt - q))) != nullptr; ++q) {  // (memchr: a byte loop over four million verdicts is 4 ms)
-            const u32 r = (u32)(q - keep);
-            const double e = exact_entropy(d, freqs + rel_pair[r], rel_pair[r + 1] - rel_pair[r]);
-            ent[r] = e;
-            const bool k = !(emax > 0 && (e < emin || e > emax));
-            keep[r] = k ? EV_KEEP : EV_DROP;
-            if (!k) ++ndrop;
-        }
+        std::vector<u32> hostpos;  // (memchr: a byte loop over four million verdicts is 4 ms)
+        hostpos.reserve(counts[1]);
+        for (u8* q = keep; (q = (u8*)memchr(q, EV_HOST, (size_t)(keep + nt - q))) != nullptr; ++q) hostpos.push_back((u32)(q - keep));
+        const u32 nh = (u32)hostpos.size();
+        unsigned nth = host_threads();
+        if (nh < 256) nth = 1;   // (libm's log twice per tuple: below that the pool's wake-up costs more)
+        const u32 per = (nh + nth - 1) / nth;
+        std::atomic<u64> dropped{0};
+        auto decide = [&](unsigned t) {
+            const u32 lo = t * per < nh ? t * per : nh, hi = lo + per < nh ? lo + per : nh;
+            u64 nd = 0;
+            for (u32 i = lo; i < hi; ++i) {
+                const u32 r = hostpos[i];
+                const double e = exact_entropy(d, freqs + rel_pair[r], rel_pair[r + 1] - rel_pair[r]);
+                ent[r] = e;
+                const bool k = !(emax > 0 && (e < emin || e > emax));
+                keep[r] = k ? EV_KEEP : EV_DROP;
+                if (!k) ++nd;
+            }
+            if (nd) dropped += nd;
+        };
+        if (nth > 1) pool.run(nth, decide); else decide(0u);
+        ndrop += dropped.load();
     }
     static const bool tl_on = getenv("DSM_TIMELINE") != nullptr;
     if (tl_on) { char msg[96]; snprintf(msg, sizeof msg, "nt=%u dropped=%llu host=%u", nt, (unsigned long long)ndrop, counts[1]); timeline("  emitter: verdicts", msg); }
@@ -1711,12 +1764,13 @@ static int emit_job(HostPool& pool, EmitSet& E, int c, u32 d, double emin, doubl
         const size_t ns = seg.size() / 2;
         std::vector<u32> bp(ns), bq(ns);
         for (size_t i = 0; i < ns; ++i) { bp[i] = rel_path[seg[2 * i]]; bq[i] = rel_pair[seg[2 * i]]; }
+        // (one pair per tuple: a run's pair offsets are again 0, 1, 2, ... -- the start of the shared array, which is left as it is)
         unsigned nth = host_threads();
         if (nt < 65536) nth = 1;
         const u32 per = (nt + nth - 1) / nth;
         auto rebase = [&](unsigned t) {   // entries lo .. hi - 1 of this thread (the last one takes the closing entry nt)
             const u32 lo = t * per < nt ? t * per : nt, hi = t + 1 == nth ? nt + 1 : (lo + per < nt ? lo + per : nt);
-            rebase_runs(rel_path, rel_pair, seg, bp, bq, lo, hi);
+            rebase_runs(rel_path, one_pair ? nullptr : rel_pair, seg, bp, bq, lo, hi);
         };
         pool.run(nth, rebase);
         clock_gettime(CLOCK_MONOTONIC, &t1);
@@ -1724,12 +1778,12 @@ static int emit_job(HostPool& pool, EmitSet& E, int c, u32 d, double emin, doubl
         for (size_t i = 0; i < ns; ++i) {
             const u32 a = seg[2 * i], n = seg[2 * i + 1] - a;
             *n_tuples += n;
-            *n_pairs += rel_pair[a + n];
+            *n_pairs += one_pair ? n : rel_pair[a + n];
             if (!sink) continue;
             dsm_tuple_batch bt;
             bt.ntuples = n;
             bt.path_off = rel_path + a; bt.path_bytes = paths + bp[i]; bt.entropy = ent + a;
-            bt.pair_off = rel_pair + a; bt.ids = ids + bq[i]; bt.freqs = freqs + bq[i];
+            bt.pair_off = one_pair ? rel_pair : rel_pair + a; bt.ids = ids + bq[i]; bt.freqs = freqs + bq[i];
             if (sink(ctx, &bt)) return 1;
         }
         return 0;
@@ -1933,6 +1987,7 @@ struct Emitter {
     dsm_tuple_sink sink = nullptr;
     void* ctx = nullptr;
     std::vector<u32> zero_ids;  // the ids of a single sample's batches (emit_job)
+    std::vector<u32> iota;      // and their pair offsets: 0, 1, 2, ...
     // text mode (dsm_miner_mine_text): the chunks leave the card as the reference server's lines (textemit.h); nothing binary is copied
     dsm_text_sink text_sink = nullptr;
     TextEmit* te = nullptr;
@@ -1977,7 +2032,7 @@ struct Emitter {
                 timeline("  emitter: chunk landed");
                 if (!rc && set[k].cb[c + 1] > set[k].cb[c]) {
                     if (text_sink) rc = text_job(set[k], set[k].cb[c], set[k].cb[c + 1], &t, &pq, &m);
-                    else rc = emit_job(pool, set[k], c, d, emin, emax, sink, ctx, zero_ids, &t, &pq, &m);
+                    else rc = emit_job(pool, set[k], c, d, emin, emax, sink, ctx, zero_ids, iota, &t, &pq, &m);
                 }
                 timeline("  emitter: chunk through the sink");
             }
@@ -2148,6 +2203,7 @@ class Engine {
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         if (fill_done) (void)hipEventDestroy(fill_done);
         for (auto e : chunk_filled) if (e) (void)hipEventDestroy(e);
+        if (bounds_landed) (void)hipEventDestroy(bounds_landed);
     }
 
     template <class T> int dalloc(T*& p, size_t n) {
@@ -2586,6 +2642,10 @@ class Engine {
         timeline("levels done", w.prefix.c_str());
         if (int rc = flush_pending()) return rc;  // (a prefix that never got wide or deep)
         if (int rc = finish_prefix(w, tsink, bsink, ctx)) return rc;
+        if (w.o.last && pend.submit) {  // nothing follows that the copies could disturb or that could hide them: they go out beside the fills
+            DSM_HIP(hipEventSynchronize(bounds_landed));
+            if (int rc = flush_pending()) return rc;
+        }
         return read_back(w);
     }
 
@@ -3237,6 +3297,9 @@ class Engine {
         const bool text_mode = text_sink_ != nullptr;  // the emitter formats the chunks on the card: no binary copies, no pinned arrays
         // one sample, binary batches: every tuple has one pair, the pair offset of rank r is r -- no pair counts, no scan of them
         const bool one_pair = d == 1 && !text_mode;
+        // ... and its entropy follows from its frequency on the host; with 32-bit positions of an index that frequency fits four bytes
+        // (a parsed stream's frequencies are whatever its varints say)
+        const bool narrow = one_pair && sizeof(P) == 4 && !trie_mode;
         // top-down: start offsets (two rolling arrays); every candidate's post-order rank, and its slot and sizes at that rank
         u32* npair = nullptr;
         if (!one_pair) EARENA_GET(npair, u32, nt);
@@ -3297,15 +3360,18 @@ class Engine {
         u32* d_bounds;
         EARENA_GET(d_bounds, u32, 2 * (EmitSet::MAX_CHUNKS + 1));
         hipLaunchKernelGGL(chunk_bounds_kernel, dim3(1), dim3(64), 0, st, cbs, path_off, pair_off, d_bounds);  // after the two sentinel copies
-        // the host needs the boundaries only in flush_pending, after read_back's synchronisation; nothing else writes h_bounds meanwhile
+        // the host needs the boundaries only in flush_pending: after read_back's synchronisation, or in the last run of a call after
+        // bounds_landed, while the fills are still running; nothing else writes h_bounds meanwhile
         DSM_HIP(hipMemcpyAsync(h_bounds, d_bounds, 2 * (cbs.n + 1) * sizeof(u32), hipMemcpyDeviceToHost, st));
+        if (!bounds_landed) DSM_HIP(hipEventCreateWithFlags(&bounds_landed, hipEventDisableTiming));
+        DSM_HIP(hipEventRecord(bounds_landed, st));
         // one sample: every id is 0 -- no id array on the card or the bus (the emitter hands the sink zeros of its own)
         const bool no_ids = d == 1;
         if (!no_ids) { if (int rc = E.dev[2].ensure((size_t)npairs * 4)) return rc; }
-        if (int rc = E.dev[3].ensure((size_t)npairs * 8)) return rc;
+        if (!narrow) { if (int rc = E.dev[3].ensure((size_t)npairs * 8)) return rc; }
         if (int rc = E.dev[4].ensure((size_t)path_bytes)) return rc;
         u32* d_ids = no_ids ? nullptr : (u32*)E.dev[2].p;
-        u64* d_freqs = (u64*)E.dev[3].p;
+        u64* d_freqs = narrow ? nullptr : (u64*)E.dev[3].p;
         char* d_paths = (char*)E.dev[4].p;
         emitter.text_sink = text_sink_;
         FillVerdict fv;
@@ -3313,17 +3379,21 @@ class Engine {
         if (!text_mode) {
             const size_t nrel = (size_t)nt + EmitSet::MAX_CHUNKS + 1;
             if (int rc = E.pin[0].ensure(nrel * 4)) return rc;
-            if (int rc = E.pin[1].ensure(nrel * 4)) return rc;
+            if (!one_pair) { if (int rc = E.pin[1].ensure(nrel * 4)) return rc; }
             if (!no_ids) { if (int rc = E.pin[2].ensure((size_t)npairs * 4)) return rc; }
             if (int rc = E.pin[3].ensure((size_t)npairs * 8)) return rc;
             if (int rc = E.pin[4].ensure((size_t)path_bytes)) return rc;
             if (int rc = E.pin[5].ensure((size_t)nt * 8)) return rc;
             if (int rc = E.pin[6].ensure((size_t)nt)) return rc;
             if (int rc = E.pin[9].ensure(2 * EmitSet::MAX_CHUNKS * sizeof(u32))) return rc;
-            if (int rc = E.dev[5].ensure((size_t)nt * 8)) return rc;
+            if (!one_pair) { if (int rc = E.dev[5].ensure((size_t)nt * 8)) return rc; }
             if (int rc = E.dev[6].ensure((size_t)nt)) return rc;
             if (int rc = E.dev[7].ensure(nrel * 4)) return rc;
-            if (int rc = E.dev[8].ensure(nrel * 4)) return rc;
+            if (!one_pair) { if (int rc = E.dev[8].ensure(nrel * 4)) return rc; }
+            if (narrow) {
+                if (int rc = E.pin[10].ensure((size_t)nt * 4)) return rc;
+                if (int rc = E.dev[10].ensure((size_t)nt * 4)) return rc;
+            }
             if (int rc = E.dev[9].ensure(2 * EmitSet::MAX_CHUNKS * sizeof(u32))) return rc;
             if (!d_terms) {  // the tables of the exact entropy, once per miner (8.5 MB)
                 if (int rc = dalloc(d_terms, (size_t)TERM_TAB)) return rc;
@@ -3332,10 +3402,13 @@ class Engine {
                 DSM_HIP(hipMemcpyAsync(d_logn, logn_table(), (size_t)LOGN_TAB * 8, hipMemcpyHostToDevice, st));
             }
             DSM_HIP(hipMemsetAsync(E.dev[9].p, 0, 2 * EmitSet::MAX_CHUNKS * sizeof(u32), st));
-            fv.ent = (double*)E.dev[5].p; fv.keep = (u8*)E.dev[6].p; fv.rel_path = (u32*)E.dev[7].p; fv.rel_pair = (u32*)E.dev[8].p;
+            fv.keep = (u8*)E.dev[6].p; fv.rel_path = (u32*)E.dev[7].p;
+            if (!one_pair) { fv.ent = (double*)E.dev[5].p; fv.rel_pair = (u32*)E.dev[8].p; }
+            if (narrow) fv.freq32 = (u32*)E.dev[10].p;
             fv.terms = d_terms; fv.logn = d_logn; fv.d = d; fv.emin = prm.emin; fv.emax = prm.emax; fv.bounds = d_bounds;
         }
         E.nchunk = cbs.n;
+        E.one_pair = one_pair; E.narrow = narrow;
         // One fill per chunk of output ranks (a thread per tuple of the chunk), so that a chunk is on its way to the host while the next
         // one is being filled -- what shows at the end of a pass, where nothing else hides the last prefix's copy.
         if (!copy_stream) DSM_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
@@ -3361,7 +3434,8 @@ class Engine {
         *ready = true;
         return 0;
     }
-    // what finish_mine held back (see there): the chunks' copies, then the emitter
+    // what finish_mine held back (see there): the chunks' copies, then the emitter.  (The last run of a call holds nothing back: run
+    // calls this as soon as the boundaries have landed, and every copy waits on the copy stream for its chunk's fill.)
     struct PendingEmit {
         EmitSet* E = nullptr;
         int nchunk = 0;
@@ -3384,23 +3458,35 @@ class Engine {
                 continue;
             }
             DSM_HIP(hipStreamWaitEvent(copy_stream, chunk_filled[c], 0));
-            // (the path / pair offsets of the chunk boundaries: copied by finish_mine, landed by read_back's synchronisation)
+            // (the path / pair offsets of the chunk boundaries: copied by finish_mine, landed by read_back's synchronisation or bounds_landed)
             const u64 pb0 = h_bounds[2 * c], qb0 = h_bounds[2 * c + 1], pb1 = h_bounds[2 * (c + 1)], qb1 = h_bounds[2 * (c + 1) + 1];
             // offsets relative to the chunk (its own closing entry included), entropies, verdicts, the chunk's counts
-            DSM_HIP(hipMemcpyAsync((u32*)E.pin[0].p + t0 + c, (const u32*)E.dev[7].p + t0 + c, ((size_t)(t1 - t0) + 1) * 4, hipMemcpyDeviceToHost, copy_stream));
-            DSM_HIP(hipMemcpyAsync((u32*)E.pin[1].p + t0 + c, (const u32*)E.dev[8].p + t0 + c, ((size_t)(t1 - t0) + 1) * 4, hipMemcpyDeviceToHost, copy_stream));
+            // (one pair per tuple: no pair offsets and no entropies, see EmitSet::one_pair; narrow: the frequencies as four bytes, qb0 == t0)
+            u64 bytes = 0;
+            auto to_host = [&](void* dst, const void* src, size_t n) {
+                bytes += n;
+                return hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, copy_stream);
+            };
+            DSM_HIP(to_host((u32*)E.pin[0].p + t0 + c, (const u32*)E.dev[7].p + t0 + c, ((size_t)(t1 - t0) + 1) * 4));
+            if (!E.one_pair) DSM_HIP(to_host((u32*)E.pin[1].p + t0 + c, (const u32*)E.dev[8].p + t0 + c, ((size_t)(t1 - t0) + 1) * 4));
             if (t1 > t0) {
-                DSM_HIP(hipMemcpyAsync((double*)E.pin[5].p + t0, (const double*)E.dev[5].p + t0, (size_t)(t1 - t0) * 8, hipMemcpyDeviceToHost, copy_stream));
-                DSM_HIP(hipMemcpyAsync((u8*)E.pin[6].p + t0, (const u8*)E.dev[6].p + t0, (size_t)(t1 - t0), hipMemcpyDeviceToHost, copy_stream));
+                if (!E.one_pair) DSM_HIP(to_host((double*)E.pin[5].p + t0, (const double*)E.dev[5].p + t0, (size_t)(t1 - t0) * 8));
+                DSM_HIP(to_host((u8*)E.pin[6].p + t0, (const u8*)E.dev[6].p + t0, (size_t)(t1 - t0)));
             }
-            DSM_HIP(hipMemcpyAsync((u32*)E.pin[9].p + 2 * c, (const u32*)E.dev[9].p + 2 * c, 2 * sizeof(u32), hipMemcpyDeviceToHost, copy_stream));
+            DSM_HIP(to_host((u32*)E.pin[9].p + 2 * c, (const u32*)E.dev[9].p + 2 * c, 2 * sizeof(u32)));
             E.pb[c] = pb0; E.qb[c] = qb0;
             if (qb1 > qb0) {
-                if (pend.ids) DSM_HIP(hipMemcpyAsync((u32*)E.pin[2].p + qb0, d_ids + qb0, (qb1 - qb0) * 4, hipMemcpyDeviceToHost, copy_stream));
-                DSM_HIP(hipMemcpyAsync((u64*)E.pin[3].p + qb0, d_freqs + qb0, (qb1 - qb0) * 8, hipMemcpyDeviceToHost, copy_stream));
+                if (pend.ids) DSM_HIP(to_host((u32*)E.pin[2].p + qb0, d_ids + qb0, (qb1 - qb0) * 4));
+                if (E.narrow) DSM_HIP(to_host((u32*)E.pin[10].p + qb0, (const u32*)E.dev[10].p + qb0, (qb1 - qb0) * 4));
+                else DSM_HIP(to_host((u64*)E.pin[3].p + qb0, d_freqs + qb0, (qb1 - qb0) * 8));
             }
-            if (pb1 > pb0) DSM_HIP(hipMemcpyAsync((char*)E.pin[4].p + pb0, d_paths + pb0, pb1 - pb0, hipMemcpyDeviceToHost, copy_stream));
+            if (pb1 > pb0) DSM_HIP(to_host((char*)E.pin[4].p + pb0, d_paths + pb0, pb1 - pb0));
             DSM_HIP(hipEventRecord(E.cready[c], copy_stream));
+            if (timeline_on()) {
+                char msg[96];
+                snprintf(msg, sizeof msg, "chunk %d: %u tuples, %llu bytes", c, t1 - t0, (unsigned long long)bytes);
+                timeline("copies queued", msg);
+            }
         }
         DSM_HIP(hipEventRecord(E.ready, copy_stream));
         emitter.submit();
@@ -3411,6 +3497,7 @@ class Engine {
     double* d_logn = nullptr;
     hipEvent_t fill_done = nullptr;
     hipEvent_t chunk_filled[EmitSet::MAX_CHUNKS] = {nullptr};
+    hipEvent_t bounds_landed = nullptr;  // h_bounds holds the pending set's chunk boundaries (finish_mine)
 
     // wait for the emitter and fold its counters into stats
     int finish_emits() {
@@ -3592,6 +3679,7 @@ struct MinerT : MinerBase {
         shallow.expand_cap = k + 1;
         shallow.capture = &cap;
         shallow.count = false;
+        shallow.last = false;  // (of a split prefix's runs the last one is `top`)
         rc = e.run(prefix.c_str(), ts, nullptr, ctx, shallow);
         if (rc) return rc;
         for (size_t q = 0; q < cap.sym.size(); ++q) {
@@ -3601,6 +3689,7 @@ struct MinerT : MinerBase {
             RunOpts below = o;
             below.emit_lo = k + 1;
             below.seed = &sub;
+            below.last = false;
             rc = run_auto(prefix + "ACGT"[cap.sym[q]], ts, ctx, below);
             if (rc) return rc;
         }
@@ -3666,6 +3755,7 @@ struct MinerT : MinerBase {
             else {
                 RunOpts o;
                 o.emit = mine;
+                o.last = k + 1 == n;
                 rc = run_auto(prefixes[k] ? prefixes[k] : "", ts, ctx, o);
             }
         }

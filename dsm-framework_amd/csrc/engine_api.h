@@ -48,6 +48,7 @@ struct RunOpts {
     const NodeOrder* seed = nullptr;   // the order of the node at seed->depth
     NodeOrder* capture = nullptr;      // receives the symbols and orders of the nodes at capture->depth
     bool count = true;                 // `reported` counts the nodes of the depths emit_lo..emit_hi (not in a shallow pass)
+    bool last = false;                 // the last run of a call: no next prefix hides its tuples' copies, they start as early as they can
 };
 
 // ---- the server side's engine runs (dsm_server, server.hip) ----
