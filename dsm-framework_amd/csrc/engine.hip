@@ -43,6 +43,7 @@
 #include "engine_api.h"
 #include "emit_runs.h"
 #include "emit_fill.h"
+#include "ranges.h"
 
 namespace dsm {
 
@@ -639,85 +640,281 @@ __global__ __launch_bounds__(256) void advance_wave_kernel(Xchg x, AdvanceOut o)
     }
 }
 
+// ---------------------------------------------------------------------------------------------
 // The down-sweep of ONE sample that is mined (no links, no reader counts, no stream records: path words and record handles only), the
-// case BASELINE's metric is quoted on.  advance_wave_kernel handles every mode with run-time flags and spends ~420 instructions per
-// wave of 64 parents -- more scalar than vector ones: the sweep is bound by their issue, not by the 21 bytes per node it moves.  Here a
-// WAVE takes a whole tile of 256 parents: the tile's four plane lines arrive through scalar loads, the counts before each of its four
-// rounds are scalar sums, no LDS and no barrier; the parents' path words of all four rounds are requested before the first is used.
+// case BASELINE's metric is quoted on.  Two launches between two LF-step launches: range_sums_kernel, advance_single_kernel.
+//
+// The level's tiles are cut into ranges (ranges.h): one workgroup per range, each of its waves a quarter of it, front to back.  What a
+// wave needs to know is where its first tile's children start, per symbol -- the children before its tiles.  range_sums_kernel adds
+// up the child counts (and the candidates) of every wave's tiles and of every range from the lines the LF-step kernel wrote; every
+// workgroup of the sweep then adds up the sums of the ranges before its own by itself, as scan_down_kernel<RAW> does with the sums
+// of its tiles: a few KB that sit in L2, read after the launch that wrote them has ended.  No workgroup waits for another one.
+// There are no per-tile counts and no scan of them: a wave keeps the running offsets of its tiles in scalar registers.
 // (the line of a round, written by the LF-step kernel: {plane[4], candidate bits, candidates | pairs << 32, -, -}, ExpandArgs::symbol_phase)
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ u32 wave_sum_u32(u32 v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+__device__ __forceinline__ u32 uniform_u32(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
+// word held by lane `l` (a constant) as a wave-uniform value
+__device__ __forceinline__ u64 lane_word(u64 v, int l) {
+    return (u64)(u32)__builtin_amdgcn_readlane((int)(u32)v, l) | ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(v >> 32), l) << 32);
+}
+
+constexpr u32 RANGE_ROWS = 5;  // children with symbol 0..3, candidates
+constexpr u32 LEAN_PUB = 2;    // the sweep's two words for publish_kernel: d_totals[2], d_totals[3]
+#ifndef DSM_ADVANCE_RMAX
+#define DSM_ADVANCE_RMAX 1024   // ranges of a level at most: four workgroups per CU
+#endif
+// DSM_ADVANCE_RANGES: fewer ranges at most (a test hook: a level of a few dozen tiles then has many tiles per wave, uneven ranges, empty waves)
+static inline u32 advance_rmax() {
+    static const u32 rmax = [] {
+        const char* e = getenv("DSM_ADVANCE_RANGES");
+        const long v = e ? atol(e) : 0;
+        return v >= 1 && v < (long)DSM_ADVANCE_RMAX ? (u32)v : (u32)DSM_ADVANCE_RMAX;
+    }();
+    return rmax;
+}
+
+// sub[(4 * b + w) * 5 + row]: sums of the tiles of wave w of range b;  rsum[row * R + b]: sums of range b (R = workgroups launched)
+// fold == 0: nobody reads the candidates' row (word 5 of a line need not have been written): it is left 0
+__global__ __launch_bounds__(256) void range_sums_kernel(const u64* __restrict__ kplane, u32 nw, u32 nbp, u32 T, u32 fold, u32* __restrict__ sub,
+                                                         u32* __restrict__ rsum) {
+    __shared__ u32 ws[RANGE_WAVES][RANGE_ROWS];
+    const u32 lane = threadIdx.x & 63, wi = uniform_u32(threadIdx.x >> 6), b = blockIdx.x, R = gridDim.x;
+    u32 t0, t1;
+    range_wave_tiles(T, nbp, b, wi, &t0, &t1);
+    // a tile is 4 lines of 8 words: lane -> word (lane & 7) of line (lane >> 3) & 3 of the tile; the halves of the wave take two tiles
+    const u32 j = lane & 7u, ql = (lane >> 3) & 3u, half = lane >> 5;
+    u32 s = 0;   // lanes with j < 4: children with symbol j; j == 5: candidates
+    for (u32 tb = t0; tb < t1; tb += 8) {
+        u64 v[4];
+        bool ok[4];
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) {
+            const u32 t = tb + 2 * k + half, w = t * 4 + ql;
+            ok[k] = t < t1 && w < nw;   // (lines of waves beyond the level's last do not exist)
+            v[k] = kplane[(size_t)(ok[k] ? w : 0u) * 8 + j];
+        }
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k)
+            if (ok[k]) s += j < 4 ? (u32)__popcll(v[k]) : (u32)v[k];
+    }
+    s += __shfl_xor(s, 8, 64);
+    s += __shfl_xor(s, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    if (lane < 4 || lane == 5) {
+        const u32 row = lane < 4 ? lane : 4u;
+        if (row == 4 && !fold) s = 0;
+        ws[wi][row] = s;
+        sub[((size_t)b * RANGE_WAVES + wi) * RANGE_ROWS + row] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < RANGE_ROWS) rsum[(size_t)threadIdx.x * R + b] = ws[0][threadIdx.x] + ws[1][threadIdx.x] + ws[2][threadIdx.x] + ws[3][threadIdx.x];
+}
+
+// The sweep.  A wave takes a tile of 256 parents at a time: the tile's four lines arrive as one vector load (lane -> word) and
+// are handed round as scalars; the counts before each of its four rounds are scalar sums, no LDS and no barrier inside the walk.  While
+// a tile's children are stored, the requests of the next one are in flight: its lines, its parents' path words and, where the sweep
+// stores the candidates, its nodes' frequencies.  Every load is unconditional and clamped to a valid address.
+// pub[0] = width of the new level, pub[1] = width + candidates (what the scan's totals were: PublishArgs::total / grand)
 template <typename P>
-__global__ __launch_bounds__(256) void advance_single_kernel(Xchg x, AdvanceOut o) {
+__global__ __launch_bounds__(256) void advance_single_kernel(Xchg x, AdvanceOut o, u32 T, const u32* __restrict__ sub, const u32* __restrict__ rsum,
+                                                             u32* __restrict__ pub) {
+    constexpr u32 RING = 128;
+    __shared__ u32 red[RANGE_WAVES][4];
+    __shared__ u32 ring_r[RANGE_WAVES][4][RING];     // record handles of the children that wait, per wave and symbol
+    __shared__ uint2 ring_p[RANGE_WAVES][4][RING];   // their path words
     const int lane = threadIdx.x & 63;
     const u32 F = (u32)x.F;
     const u32 nw = (F + 63) >> 6;
-    const u32 tile = (u32)__builtin_amdgcn_readfirstlane((int)(xcd_block() * 4 + (threadIdx.x >> 6)));
-    if (tile >= o.nbp) return;
-    const u64 lt = (1ull << lane) - 1;
-    const u64* __restrict__ line = o.kplane + (size_t)tile * 32;
-    // ---- requests: the parents' path words, the lines as the lanes will copy them, the tile's scanned counts ----
-    uint2 mypw[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const u32 u = (tile * 4 + (u32)q) * 64 + lane;
-        mypw[q] = o.parent_pw[u < F ? u : 0u];
-    }
-    u64 copyw = 0;
-    if (lane < 32) copyw = line[lane];
-    u32 cum[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) cum[c] = o.cnt4[(size_t)c * o.nbp + tile];
-    u64 up[4][4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) up[q][c] = tile * 4 + (u32)q < nw ? line[q * 8 + c] : 0ull;   // (planes exist for the waves that hold nodes only)
-    // ---- the retained directory of the level: planes and first-child indexes per round; the candidate words to their arrays ----
-    {
-        const u32 q = (u32)lane >> 3, j = (u32)lane & 7u, w = tile * 4 + q;
-        if (lane < 32 && w < nw) {
-            if (j < 4) o.kplane_w[(size_t)w * 4 + j] = copyw;
-            else if (o.cand_copy && j == 4) o.candbits[w] = copyw;
-            else if (o.cand_copy && j == 5) o.wsum[w] = copyw;
-        }
-    }
-    const u32 r = o.plevel & (PW_CHUNK - 1);
-    u32 kc = 0;   // lane 4q + c: index of the first child c of round q
-    u32 cbase = 0;  // (candidate store) record of the round's first candidate
-    u64 cbq[4] = {0, 0, 0, 0};   // candidate bits of the four rounds, their counts, this lane's frequencies where it is one
-    u32 ncq[4] = {0, 0, 0, 0};
-    u64 fq[4] = {0, 0, 0, 0};
-    if (o.crec) {
-        cbase = o.cnt4[(size_t)4 * o.nbp + tile] - o.cnt4[(size_t)4 * o.nbp];
+    const u32 wi = uniform_u32(threadIdx.x >> 6), R = gridDim.x, b = uniform_u32(xcd_block());
+    const bool fold = o.crec != nullptr;
+    u32 t0, t1;
+    range_wave_tiles(T, o.nbp, b, wi, &t0, &t1);
+    const u64* __restrict__ kplane = o.kplane;
+    const uint2* __restrict__ parent_pw = o.parent_pw;
+    const u32 lq = ((u32)lane >> 3) & 3u, lj = (u32)lane & 7u;
+    auto load_line = [&](u32 t) -> u64 {   // word lj of line lq of tile t (both halves of the wave hold the tile); 0 where there is none
+        const u32 w = t * 4 + lq;
+        const bool ok = t < t1 && w < nw;
+        const u64 v = kplane[(size_t)(ok ? w : 0u) * 8 + lj];
+        return ok ? v : 0ull;
+    };
+    auto load_pw = [&](u32 t, uint2 pw[4]) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            if (tile * 4 + (u32)q < nw) { cbq[q] = line[q * 8 + 4]; ncq[q] = (u32)line[q * 8 + 5]; }
-            const u32 u = (tile * 4 + (u32)q) * 64 + lane;
-            if ((cbq[q] >> lane) & 1ull) fq[q] = (u64)x_freq<P>(x, 0, u);
+            const u32 u = (t * 4 + (u32)q) * 64 + lane;
+            pw[q] = parent_pw[t < t1 && u < F ? u : 0u];
+        }
+    };
+    // The sample's frequency column (x_freq with sample 0) is read in 16-bit pieces, the same instructions whatever the level's entry
+    // width: one piece of a two-byte entry, all FP of a P.  (a piece a narrow level does not have repeats the first and is not used)
+    constexpr int FP = (int)sizeof(P) / 2;
+    const u16* __restrict__ fcol = reinterpret_cast<const u16*>(x.base + XHDR);
+    const u32 fpieces = x.fb <= 2 ? 1u : (u32)FP;
+    const u64 fmask = x.fb == 1 ? (u64)(PACK_FMAX - 1) : ~0ull;
+    auto load_freq = [&](u32 t, u32 fq[4][FP]) {   // of the tile's nodes: most rounds of 64 nodes hold a candidate where a level is filtered
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const u32 u = (t * 4 + (u32)q) * 64 + lane;
+            const u64 v = fold && t < t1 && u < F ? (u64)u : 0ull;   // (a level whose candidates are not stored here: entry 0, unused)
+            const u64 e = (x.fb == 1 ? x_word_index(x, 0, v) : v) * fpieces;
+#pragma unroll
+            for (int k = 0; k < FP; ++k) fq[q][k] = (u32)fcol[e + ((u32)k < fpieces ? (u32)k : 0u)];
+        }
+    };
+    auto freq_of = [&](const u32 fq[FP]) -> u64 {
+        u64 f = fq[0];
+#pragma unroll
+        for (int k = 1; k < FP; ++k) f |= (u32)k < fpieces ? (u64)fq[k] << (16 * k) : 0ull;
+        return f & fmask;
+    };
+    // ---- requests of the first tile, then the offsets of this wave while they are under way ----
+    u64 line_a = load_line(t0);
+    uint2 pw_a[4];
+    load_pw(t0, pw_a);
+    u32 fq_a[4][FP];
+    load_freq(t0, fq_a);
+    // wave wi adds up row wi of the range sums (children with symbol wi), all four a quarter of the candidates' row; sixteen requests
+    // of a lane at a time: one round trip for up to 1024 ranges
+    u32 all = 0, bef = 0, call = 0, cbef = 0;
+    for (u32 q0 = 0; q0 < R; q0 += 1024) {
+        u32 v[16], vc[4];
+#pragma unroll
+        for (u32 k = 0; k < 16; ++k) {
+            const u32 q = q0 + 64 * k + (u32)lane;
+            v[k] = rsum[(size_t)wi * R + (q < R ? q : 0u)];
+        }
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) {
+            const u32 q = q0 + 256 * k + wi * 64 + (u32)lane;
+            vc[k] = rsum[(size_t)4 * R + (q < R ? q : 0u)];   // (zeros where the candidates are not stored here)
+        }
+#pragma unroll
+        for (u32 k = 0; k < 16; ++k) {
+            const u32 q = q0 + 64 * k + (u32)lane;
+            all += q < R ? v[k] : 0u;
+            bef += q < b ? v[k] : 0u;   // (b < R)
+        }
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k) {
+            const u32 q = q0 + 256 * k + wi * 64 + (u32)lane;
+            call += q < R ? vc[k] : 0u;
+            cbef += q < b ? vc[k] : 0u;
         }
     }
+    u32 sb[3][RANGE_ROWS];   // the sub-range sums of this range's first three waves
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const u32 w = tile * 4 + (u32)q, u = w * 64 + lane;
-        const uint2 ppw = mypw[q];
-        if (o.crec && cbq[q]) {   // this round's candidates: node, frequency (metaserver.cpp:472-484 prints id:frequency; one sample: id 0)
-            const u32 k = cbase + bits_below_lane(cbq[q]);
-            if (((cbq[q] >> lane) & 1ull) && k < o.crec_cap) o.crec[k] = make_uint4(u, 0u, (u32)fq[q], (u32)(fq[q] >> 32));
+    for (u32 k = 0; k < 3; ++k)
+#pragma unroll
+        for (u32 c = 0; c < RANGE_ROWS; ++c) sb[k][c] = sub[((size_t)b * RANGE_WAVES + k) * RANGE_ROWS + c];
+    all = wave_sum_u32(all); bef = wave_sum_u32(bef); call = wave_sum_u32(call); cbef = wave_sum_u32(cbef);
+    if (lane == 0) { red[wi][0] = all; red[wi][1] = bef; red[wi][2] = call; red[wi][3] = cbef; }
+    __syncthreads();
+    u32 cum[4];      // index of the first child with symbol c of the wave's next round
+    u32 cbase = 0;   // record of its first candidate
+    u32 width = 0, ncand = 0;
+    {
+        u32 seg = 0;
+#pragma unroll
+        for (u32 c = 0; c < 4; ++c) {
+            u32 before = red[c][1];
+#pragma unroll
+            for (u32 k = 0; k < 3; ++k) before += k < wi ? sb[k][c] : 0u;
+            cum[c] = uniform_u32(seg + before);
+            seg += red[c][0];
+            ncand += red[c][2];
+            cbase += red[c][3];
         }
-        cbase += ncq[q];
+        width = seg;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const u64 m = up[q][c];
-            if (lane == q * 4 + c) kc = cum[c];
-            const u32 below = bits_below_lane(m);
-            const u32 vj = cum[c] + below;
-            if (((m >> lane) & 1ull) && vj < o.cap) {
-                o.rp0[vj] = (u32)c * o.seg + w * 64u + below;
-                o.pw[vj] = r == 0 ? make_uint2(u, (u32)c) : make_uint2(ppw.x, ppw.y | ((u32)c << (2 * r)));
+        for (u32 k = 0; k < 3; ++k) cbase += k < wi ? sb[k][4] : 0u;
+        cbase = uniform_u32(cbase);
+    }
+    if (b == R - 1 && threadIdx.x == 0) { pub[0] = width; pub[1] = width + ncand; }
+    if (t0 >= t1) return;
+    const u32 r = o.plevel & (PW_CHUNK - 1);
+    u32* __restrict__ rp0 = o.rp0;
+    uint2* __restrict__ pwout = o.pw;
+    // The children of a symbol leave the wave 64 at a time, at multiples of 64 entries: a round has some sixteen of a symbol, and a store
+    // instruction of sixteen lanes takes the memory pipeline as long as one of sixty-four.  Entry vj waits in slot vj mod 128 of the
+    // wave's ring of its symbol (a round adds at most 64 to the less than 64 that wait); the lanes that wrote the slots and the lanes
+    // that read them belong to one wave, whose LDS accesses complete in program order.
+    u32 fl[4];   // first entry of symbol c that has not been stored
+#pragma unroll
+    for (int c = 0; c < 4; ++c) fl[c] = cum[c];
+    auto flush = [&](int c, u32 from, u32 to) {   // entries [from, to) of the 64 around `from`
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // (orders the compiler's view of the ring; no instruction at this scope)
+        __builtin_amdgcn_wave_barrier();
+        const u32 i = (from & ~63u) + (u32)lane;
+        const u32 v = ring_r[wi][c][i & (RING - 1)];
+        const uint2 p = ring_p[wi][c][i & (RING - 1)];
+        if (i >= from && i < to && i < o.cap) {   // a level wider than the window is reported through the total, not written
+            rp0[i] = v;
+            pwout[i] = p;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+    for (u32 tile = t0; tile < t1; ++tile) {
+        // ---- requests of the next tile: its lines, its parents' path words, its nodes' frequencies ----
+        const u64 line_b = load_line(tile + 1);
+        uint2 pw_b[4];
+        load_pw(tile + 1, pw_b);
+        u32 fq_b[4][FP];
+        load_freq(tile + 1, fq_b);
+        // ---- the retained directory of the level: planes per round, the candidate words to their arrays ----
+        {
+            const u32 w = tile * 4 + lq;
+            if (lane < 32 && w < nw) {
+                if (lj < 4) o.kplane_w[(size_t)w * 4 + lj] = line_a;
+                else if (o.cand_copy && lj == 4) o.candbits[w] = line_a;
+                else if (o.cand_copy && lj == 5) o.wsum[w] = line_a;
             }
-            cum[c] += (u32)__popcll(m);
+        }
+        u32 kc = 0;   // lane 4q + c: index of the first child c of round q
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const u32 w = tile * 4 + (u32)q, u = w * 64 + lane;
+            const uint2 ppw = pw_a[q];
+            if (fold) {   // this round's candidates: node, frequency (metaserver.cpp:472-484 prints id:frequency; one sample: id 0)
+                const u64 cb = lane_word(line_a, q * 8 + 4);
+                const u32 k = cbase + bits_below_lane(cb);
+                const u64 f = freq_of(fq_a[q]);
+                if (((cb >> lane) & 1ull) && k < o.crec_cap) o.crec[k] = make_uint4(u, 0u, (u32)f, (u32)(f >> 32));
+                cbase += (u32)__builtin_amdgcn_readlane((int)(u32)line_a, q * 8 + 5);
+            }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const u64 m = lane_word(line_a, q * 8 + c);
+                if (lane == q * 4 + c) kc = cum[c];
+                const u32 below = bits_below_lane(m);
+                const u32 vj = cum[c] + below;
+                if ((m >> lane) & 1ull) {
+                    ring_r[wi][c][vj & (RING - 1)] = (u32)c * o.seg + w * 64u + below;
+                    ring_p[wi][c][vj & (RING - 1)] = r == 0 ? make_uint2(u, (u32)c) : make_uint2(ppw.x, ppw.y | ((u32)c << (2 * r)));
+                }
+                cum[c] += (u32)__popcll(m);
+                if ((cum[c] ^ fl[c]) >> 6) {   // the 64 entries around fl[c] are complete
+                    flush(c, fl[c], cum[c]);
+                    fl[c] = (fl[c] & ~63u) + 64;
+                }
+            }
+        }
+        if (lane < 16 && tile * 4 + ((u32)lane >> 2) < nw) o.kcum[(size_t)tile * 16 + lane] = kc;
+        line_a = line_b;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            pw_a[q] = pw_b[q];
+#pragma unroll
+            for (int k = 0; k < FP; ++k) fq_a[q][k] = fq_b[q][k];
         }
     }
-    if (lane < 16 && tile * 4 + ((u32)lane >> 2) < nw) o.kcum[(size_t)tile * 16 + lane] = kc;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) flush(c, fl[c], cum[c]);   // what is left: less than 64 entries per symbol, none across a multiple of 64
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2401,7 +2598,7 @@ class Engine {
         DSM_HIP(hipMemcpy(d_tpos_tab, tpos.data(), (size_t)nlocal * sizeof(u32*), hipMemcpyHostToDevice));
         if (int rc = dalloc(d_splane_tab, (size_t)nlocal)) return rc;
         DSM_HIP(hipMemcpy(d_splane_tab, splane.data(), (size_t)nlocal * sizeof(u64*), hipMemcpyHostToDevice));
-        if (int rc = dalloc(cnt4, 5 * ntile + 8)) return rc;   // (fifth row: candidates per tile, one sample)
+        if (int rc = dalloc(cnt4, 5 * ntile + 32)) return rc;   // (fifth row: candidates per tile, one sample; the range sweep: 5 sums per range)
         if (stream_mode)
             for (int k = 0; k < 2; ++k) if (int rc = dalloc(sa[k], (size_t)Fcap + 64)) return rc;
         if (owner_mode) {
@@ -2409,8 +2606,8 @@ class Engine {
             for (int k = 0; k < 2; ++k) if (int rc = dalloc(lite_slot[k], (size_t)Fcap + 64)) return rc;
         }
         if (d == 1 && !trie_mode) {
-            if (int rc = dalloc(cntraw, 5 * ntile + 8)) return rc;
-            DSM_HIP(hipMemset(cntraw, 0, (5 * ntile + 8) * sizeof(u32)));
+            if (int rc = dalloc(cntraw, 5 * ntile + 32)) return rc;   // (the range sweep: 5 sums per wave of a range, at most ntile / 4 + 1 ranges)
+            DSM_HIP(hipMemset(cntraw, 0, (5 * ntile + 32) * sizeof(u32)));
         }
         if (int rc = lf_step_geometry(sizeof(P) == 8, device, &lfgeo)) return rc;  // (all waves of an LF-step launch are resident)
         if (d > 1 || trie_mode) { if (int rc = dalloc(sinfo, (size_t)slots)) return rc; }
@@ -2575,6 +2772,7 @@ class Engine {
         u32* slot = nullptr;     // the window's links (self_mode)
         bool filtered = false;   // the level's output predicates are evaluated; its candidates are stored after the wait
         u32 crec_cap = 0;        // > 0: the sweep stores the level's candidates itself, up to that many records (see emit_store)
+        bool lean = false;       // the range sweep took the level (advance_single_kernel)
         u32 Fn = 0;              // the children's level: width and class, from the published packet
         bool w16 = false, w9 = false;
         bool spec_hit = false;   // the LF-step launch queued ahead of the wait took the children's level
@@ -2965,7 +3163,12 @@ class Engine {
             s.crec_cap = (u32)(room < (size_t)F ? room : (size_t)F);
         }
         const bool fold = s.crec_cap > 0;
-        if (nbp > 1) {
+        s.lean = lean;
+        const RangeGeo rg = lean ? range_geometry(nbp, advance_rmax()) : RangeGeo{0u, 0u};   // (lean: two tiles or more)
+        if (lean) {
+            // the sums of the level's ranges and of their waves' parts, from the lines its LF-step kernel wrote: all the sweep needs
+            hipLaunchKernelGGL(range_sums_kernel, dim3(rg.R), dim3(256), 0, st, splane[0], (F + 63) >> 6, nbp, rg.T, fold ? 1u : 0u, cntraw, cnt4);
+        } else if (nbp > 1) {
             // one sample: the tile counts from the planes its LF-step kernel wrote (that kernel added them up with four atomics per
             // tile of 64 nodes before: 470 K memory-side atomics per launch of the wide levels); with them the candidates per tile
             if (!merged) hipLaunchKernelGGL(lite_count_kernel, dim3((nbp + 63) / 64), dim3(256), 0, st, splane[0], (F + 63) >> 6, cntraw, nbp, 3u, fold ? 1u : 0u);
@@ -2979,7 +3182,7 @@ class Engine {
         }
         if (fold) { ao.crec = reinterpret_cast<uint4*>(carena.base + carena.off); ao.crec_cap = s.crec_cap; }
         if (nbp == 1) hipLaunchKernelGGL((advance_down_kernel<P>), dim3(1), dim3(256), 0, st, x, ao);
-        else if (lean) hipLaunchKernelGGL((advance_single_kernel<P>), dim3((nbp + 3) / 4), dim3(256), 0, st, x, ao);
+        else if (lean) hipLaunchKernelGGL((advance_single_kernel<P>), dim3(rg.R), dim3(256), 0, st, x, ao, rg.T, (const u32*)cntraw, (const u32*)cnt4, d_totals + LEAN_PUB);
         else hipLaunchKernelGGL((advance_wave_kernel<P>), dim3(nbp), dim3(256), 0, st, x, ao);
         if (s.filtered) {
             if (int erc = emit_filter(me, F, depth, x, cur, w.order_mode, !fused_filter, fold)) return erc;
@@ -2998,9 +3201,9 @@ class Engine {
         pa.total = nbp == 1 ? d_pub_tot : d_totals;  // new level's width: from the single tile, or the scan's total
         pa.cmax_base = s.x.base; pa.cmax_bpr = s.x.bpr; pa.cmax_world = (u32)world;
         if (s.filtered) pa.cand = d_totals64;
-        if (s.crec_cap) {  // the scan ran over the child counts and, behind them, the candidate counts: the width is what it had reached there
-            pa.total = cnt4 + (size_t)4 * nbp;
-            pa.grand = d_totals;
+        if (s.lean) pa.total = d_totals + LEAN_PUB;   // the range sweep's last workgroup left the width, and behind it width + candidates
+        if (s.crec_cap) {  // (the sweep stored the candidates, one pair each: their number is the difference)
+            pa.grand = d_totals + LEAN_PUB + 1;
             pa.cand = nullptr;
         }
         pa.clear = reinterpret_cast<u32*>(multi ? xsend : xrecv[nxt]);  // where the next level's expand reports its child maximum
